@@ -2,7 +2,18 @@
 """bench.py -- headline benchmark: Msamples/s of Tracer::render on the GPU.
 
     python bench.py --gpus N --steps K --warmup W [--workload C3] [--scaling weak|strong] [--backend nccl|rccl-abi|gloo]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, renders W untimed and K timed steps, and prints the headline line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step), the run's shape and `config`.  Everything else
+the line can carry -- `roofline` with its rocprofv3 counter passes and per-launch kernel times, `lens_extension`,
+`other_configs`, `cpu_baseline`, `parity`, and for N > 1 the verification step and `final_gather_only` -- is measured
+only with --full.  --dump-outputs DIR writes the frame the timed steps accumulated, as a caller of Tracer::render
+receives it, to DIR/frame.npy (float32 running sums, H x W x 4) right after the timed steps; the inputs are fixed (scene,
+seed 0x5EED, sample_base i * samples), so two builds given the same arguments can be compared array for array.  A frame
+over 64 MB (C5) is written as a fixed, seeded sample of its pixels (frame.npy, P x 4) with their row-major indices
+(frame_index.npy, float64).
 
 Both forms work for N > 1: typed from a bare shell (no WORLD_SIZE in the environment) the first one starts the second as a
 CHILD process -- one rank per GPU, rendezvous on 127.0.0.1 at a free port -- relays rank 0's JSON line and exits with the
@@ -21,25 +32,26 @@ un-permute of step i run on a second HIP stream underneath the render of step i+
 exchange, is inside the timed region.
   --scaling weak   (default) samples per step = 64 * N: fixed work per GPU.
   --scaling strong samples per step stay what the workload names (so `--workload C5 --gpus 8 --scaling strong` IS
-                   BASELINE configs[4]: 3840x2160x256 spp sharded over 8 GPUs); a second timed pass gathers only once,
-                   after the last step ("the final framebuffer"), and is reported as `final_gather_only`.
+                   BASELINE configs[4]: 3840x2160x256 spp sharded over 8 GPUs); with --full a second timed pass gathers
+                   only once, after the last step ("the final framebuffer"), and is reported as `final_gather_only`.
   --backend nccl   torch.distributed's RCCL; rccl-abi = the library's own bt_comm_* entry points (the exchange a
                    non-Python host would call); gloo = rehearsal on a box with fewer GPUs than ranks.
 
 N > 1 lines carry what a reader needs to check them: `ranks_joined` (the process group's size after init), `devices` (one
-entry per rank: device index, name, PCI bus id, host pid), `verified_vs_single_rank` (by default one extra, untimed step is
-rendered sharded + exchanged and compared bit for bit with the same step rendered by one rank alone; --no-verify skips it,
---verify-all compares the whole accumulated run instead) and a `roofline` measured on rank 0's own shard launch.
+entry per rank: device index, name, PCI bus id, host pid), `verified_vs_single_rank` (with --full or --verify one extra,
+untimed step is rendered sharded + exchanged and compared bit for bit with the same step rendered by one rank alone;
+--no-verify skips it, --verify-all compares the whole accumulated run instead) and, with --full, a `roofline` measured on
+rank 0's own shard launch.
 
-One JSON line on rank 0.  `roofline`: the kernel is VALU-bound, so `achieved` / `peak` are wave64 VALU
+One JSON line on rank 0.  `roofline` (--full): the kernel is VALU-bound, so `achieved` / `peak` are wave64 VALU
 instructions per SIMD-cycle (peak 0.5: MI355X_MICROARCH.md, 2 cycles per instruction on a SIMD-32), with the HBM
 bytes (`traffic`) and every counter MEASURED IN THIS RUN by rocprofv3 --pmc passes over the same workload
 (tools/pmc_collect.py; separate passes, FETCH_SIZE doubled per the guide) -- unless rocprofv3 is unavailable, then the
 committed summary profiles/pmc_live.json is quoted and flagged `stale` when its source hash differs from this tree.
-`cpu_baseline` (N = 1): the CPU oracle -- a C port of the reference algorithm, NOT the Rust binary -- timed on the host
+`cpu_baseline` (--full, N = 1): the CPU oracle -- a C port of the reference algorithm, NOT the Rust binary -- timed on the host
 cores on a bounded sample of the same workload.
 
-`other_configs` (N = 1 only; not part of `value`): a few renders each of BASELINE.json's other configurations on this GPU
+`other_configs` (--full, N = 1 only; not part of `value`): a few renders each of BASELINE.json's other configurations on this GPU
 -- C2, C4, C5 rendered whole on one GPU, the 1080p Cornell box -- with wall and kernel time per `Tracer::render`; C2 and C4
 also carry their own PMC-derived fractions (`roofline`), measured in this run like C3's.
 """
@@ -73,6 +85,23 @@ BYTES_PER_SEGMENT = 128        # 64-byte SoA ray state read + writt
 BYTES_PER_PIXEL = 16           # RGBA32F written once per pixel per render
 SEED = 0x5EED
 PMC_CACHE = os.path.join(ROOT, "profiles", "pmc_live.json")
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much
+DUMP_SAMPLE_PIXELS = 1 << 21   # pixels kept of a larger frame: 2 Mi x (16 B of RGBA32F + 8 B of float64 index) = 48 MiB
+
+
+def dump_outputs(torch, frame, out_dir):
+    """--dump-outputs: the running sums the timed steps left in `frame` (H x W x 4 float32 on the device) -> frame.npy;
+    over DUMP_LIMIT_BYTES, a seeded sample of its pixels + their row-major indices (frame_index.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if frame.numel() * frame.element_size() <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame.cpu().numpy())
+        return
+    npix = frame.shape[0] * frame.shape[1]
+    idx = np.sort(np.random.default_rng(SEED).choice(npix, DUMP_SAMPLE_PIXELS, replace=False))
+    px = frame.reshape(npix, 4)[torch.from_numpy(idx).to(frame.device)]
+    np.save(os.path.join(out_dir, "frame.npy"), px.cpu().numpy())
+    np.save(os.path.join(out_dir, "frame_index.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(scene_name, w, h, budget_s=15.0):
@@ -375,17 +404,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short timing of C2 / C4 / C5 / Cornell at N = 1")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (quote the committed summary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the accumulated frame to DIR/frame.npy")
+    ap.add_argument("--full", action="store_true", help="also measure what is not the headline: PMC roofline and kernel times, "
+                    "lens extension, other configurations, CPU baseline, parity figure; N > 1: verification step, final-gather pass")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity figure")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the short timing of C2 / C4 / C5 / Cornell at N = 1")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live rocprofv3 --pmc passes (quote the committed summary)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "rccl-abi", "gloo"],
                     help="rccl-abi = the library's bt_comm_* entry points; gloo = rehearsal of the N>1 path on a box with "
                          "fewer GPUs than ranks (shards staged through the host)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--no-overlap", action="store_true", help="run the frame exchange on the render stream")
-    ap.add_argument("--verify", action="store_true", help="(default for N > 1) compare one extra sharded + exchanged step with "
-                    "the same step rendered by one rank alone")
+    ap.add_argument("--verify", action="store_true", help="(default for N > 1 with --full) compare one extra sharded + exchanged "
+                    "step with the same step rendered by one rank alone")
     ap.add_argument("--no-verify", action="store_true", help="N > 1: skip the verification step")
     ap.add_argument("--verify-all", action="store_true", help="compare the whole accumulated frame of warmup + timed steps with a "
                     "one-rank render of the same steps (costs N x the timed work on every rank)")
@@ -393,6 +425,8 @@ def main():
                     help="run the N>1 code path (process group, shard, all-gather, un-permute) even with one rank")
     ap.add_argument("--print-launch", action="store_true", help="print the child command a bare `--gpus N` run would start, as JSON, and exit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.print_launch):
         # typed from a bare shell: this process becomes the launcher.  It has not imported torch, has not touched the GPU and
@@ -412,12 +446,12 @@ def main():
     scene_name, w, h, base_spp = WORKLOADS[args.workload]
     spp = base_spp * world if args.scaling == "weak" else base_spp      # weak: fixed work per GPU; strong: fixed total
 
-    # counters first: child processes under rocprofv3, while this process has not initialised the GPU yet.  N = 1: the
-    # headline workload, then C2 and C4 (BASELINE configs[1] and [3]) for `other_configs`.  N > 1: rank 0 measures ITS OWN
-    # shard launch (1/N of the tiles at this run's samples per step) before it joins the process group; the other ranks wait
-    # for it in the rendezvous.
+    # --full: counters first: child processes under rocprofv3, while this process has not initialised the GPU yet.  N = 1:
+    # the headline workload, then C2 and C4 (BASELINE configs[1] and [3]) for `other_configs`.  N > 1: rank 0 measures ITS
+    # OWN shard launch (1/N of the tiles at this run's samples per step) before it joins the process group; the other ranks
+    # wait for it in the rendezvous.
     pmc, pmc_other = None, {}
-    if rank == 0 and not args.force_dist:
+    if args.full and rank == 0 and not args.force_dist:
         shard = (0, world) if world > 1 else None
         if args.no_pmc:
             pmc = cached_pmc(args.workload if world == 1 else f"{args.workload}_shard{world}")
@@ -501,6 +535,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     elapsed, step_ms = timed(args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, frame.data, args.dump_outputs)
 
     verified, verify_mode = None, None
     if args.verify_all:
@@ -513,8 +549,8 @@ def main():
         verified = bool(torch.equal(frame.data, ref.data))
         verify_mode = f"all {args.warmup + args.steps} steps"
         del ref
-    elif dist_path and (args.verify or not args.no_verify):
-        # default for N > 1: ONE extra step, outside the timed region, rendered sharded + exchanged into a fresh frame and
+    elif dist_path and (args.verify or (args.full and not args.no_verify)):
+        # default for N > 1 with --full: ONE extra step, outside the timed region, rendered sharded + exchanged into a fresh frame and
         # by this rank alone into another; every rank compares its own gathered copy, the verdict is the AND over the ranks
         i_v = args.warmup + args.steps
         keep = ex.shard.clone()
@@ -535,24 +571,25 @@ def main():
         del got, ref, keep
 
     final_only = None
-    if dist_path and args.scaling == "strong":
+    if args.full and dist_path and args.scaling == "strong":
         # second timed pass: the shards keep accumulating, ONE exchange after the last step (the final framebuffer)
         e2, _ = timed(args.warmup + args.steps, exchange_every_step=False)
         final_only = {"value": round(w * h * spp * args.steps / e2 / 1e6, 2), "unit": "Msamples/s",
                       "ms_per_step": round(e2 / args.steps * 1e3, 4), "exchanges": 1}
 
-    # segment counts and the library's own HIP-event kernel times: replay the same renders, untimed
+    # --full: segment counts and the library's own HIP-event kernel times: replay the same renders, untimed
     kernel_ms, segments = [], []
-    for i in range(args.steps):
-        if not dist_path:
-            tracer.render(scene, cam, rc, frame, seed=SEED, sample_base=(args.warmup + i) * spp)
-        else:
-            tracer.render_shard(scene, cam, rc, ex.shard, w, h, rank, world, seed=SEED, sample_base=(args.warmup + i) * spp)
-        st = scene.last_stats()
-        kernel_ms.append(st.kernel_ms)
-        segments.append(st.segments)
-    last = scene.last_stats()
-    my_pixels = last.pixels
+    if args.full:
+        for i in range(args.steps):
+            if not dist_path:
+                tracer.render(scene, cam, rc, frame, seed=SEED, sample_base=(args.warmup + i) * spp)
+            else:
+                tracer.render_shard(scene, cam, rc, ex.shard, w, h, rank, world, seed=SEED, sample_base=(args.warmup + i) * spp)
+            st = scene.last_stats()
+            kernel_ms.append(st.kernel_ms)
+            segments.append(st.segments)
+        last = scene.last_stats()
+        my_pixels = last.pixels
 
     total_samples = w * h * spp * args.steps
     value = total_samples / elapsed / 1e6
@@ -568,33 +605,34 @@ def main():
                    "parallelism": (f"tiles{world}:{args.backend}" + ("" if args.no_overlap else "+overlapped-allgather")) if dist_path else "single"},
     }
     if rank == 0:
-        k_ms = statistics.mean(kernel_ms)
-        seg = statistics.mean(segments)
-        # template arguments <OUTPUT, LENS, RECTS, VOLS, PACKED>, as rocprofv3 prints them
-        kernel_name = "bt_render_kernel<0, false, %s, %s, %s>" % (
-            {"scene": ("false", "false"), "volume": ("false", "true"), "cloud": ("false", "true")}.get(scene_name, ("true", "false"))
-            + ("true" if last.packed else "false",))
-        roof = {"bound": "valu", "unit": "wave64 VALU instructions per SIMD-cycle", "peak": VALU_PEAK, "achieved": None,
-                "frac": None, "traffic": None, "kernel": kernel_name, "kernel_ms": round(k_ms, 4), "slices": last.slices,
-                "workgroups": last.workgroups, "packed": bool(last.packed),
-                "launches_per_step": last.launches, "scratch_bytes": last.scratch_bytes,
-                "render_stream_ms_per_step_timed_region": round(statistics.mean(step_ms), 4),
-                "segments_per_launch": int(seg), "segments_per_sample": round(seg / (my_pixels * spp), 4)}
-        roof.update(pmc_fractions(pmc, k_ms))
-        # SURVEY 8(d)'s byte model, kept as a labelled non-headline figure: a wavefront formulation would move these bytes,
-        # the shipped register-resident kernel does not
-        alg_bytes = BYTES_PER_SEGMENT * seg + BYTES_PER_PIXEL * my_pixels
-        roof["model"] = {"bytes_per_launch": int(alg_bytes), "model_frac": round(alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "note": "SURVEY 8(d) wavefront byte model (128 B per path segment + 16 B per pixel) over kernel time / "
-                                 "8 TB/s; NOT traffic of this kernel, which keeps ray state in registers -- see `traffic`"}
-        roof["note"] = ("VALU-bound path tracer: frac = measured wave64 VALU instructions per SIMD-cycle / 0.5 (every instruction at "
-                        "the guide's 2 cycles: the lower bound); issue_cost_guide_frac = the guide's prices (2 plain, 4 transcendental "
-                        "and half-rate integer); issue_cost_weighted_frac = the PMC opcode classes x the mixed-stream issue cycles "
-                        "measured by tools/valu_microbench.hip (profiles/valu_issue_costs.json: the upper end; "
-                        "issue_cost_pure_stream_bound prices every opcode as a stream of its own and can exceed 1); fp32_flop_frac = "
-                        "FP32 operations on active lanes / 157.3 TF/s; hbm_measured_frac = PMC bytes / kernel time / 8 TB/s"
-                        + ("; N > 1: counters of rank 0's own shard launch, taken before it joined the process group" if world > 1 else ""))
-        out["roofline"] = roof
+        if args.full:
+            k_ms = statistics.mean(kernel_ms)
+            seg = statistics.mean(segments)
+            # template arguments <OUTPUT, LENS, RECTS, VOLS, PACKED>, as rocprofv3 prints them
+            kernel_name = "bt_render_kernel<0, false, %s, %s, %s>" % (
+                {"scene": ("false", "false"), "volume": ("false", "true"), "cloud": ("false", "true")}.get(scene_name, ("true", "false"))
+                + ("true" if last.packed else "false",))
+            roof = {"bound": "valu", "unit": "wave64 VALU instructions per SIMD-cycle", "peak": VALU_PEAK, "achieved": None,
+                    "frac": None, "traffic": None, "kernel": kernel_name, "kernel_ms": round(k_ms, 4), "slices": last.slices,
+                    "workgroups": last.workgroups, "packed": bool(last.packed),
+                    "launches_per_step": last.launches, "scratch_bytes": last.scratch_bytes,
+                    "render_stream_ms_per_step_timed_region": round(statistics.mean(step_ms), 4),
+                    "segments_per_launch": int(seg), "segments_per_sample": round(seg / (my_pixels * spp), 4)}
+            roof.update(pmc_fractions(pmc, k_ms))
+            # SURVEY 8(d)'s byte model, kept as a labelled non-headline figure: a wavefront formulation would move these bytes,
+            # the shipped register-resident kernel does not
+            alg_bytes = BYTES_PER_SEGMENT * seg + BYTES_PER_PIXEL * my_pixels
+            roof["model"] = {"bytes_per_launch": int(alg_bytes), "model_frac": round(alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             "note": "SURVEY 8(d) wavefront byte model (128 B per path segment + 16 B per pixel) over kernel time / "
+                                     "8 TB/s; NOT traffic of this kernel, which keeps ray state in registers -- see `traffic`"}
+            roof["note"] = ("VALU-bound path tracer: frac = measured wave64 VALU instructions per SIMD-cycle / 0.5 (every instruction at "
+                            "the guide's 2 cycles: the lower bound); issue_cost_guide_frac = the guide's prices (2 plain, 4 transcendental "
+                            "and half-rate integer); issue_cost_weighted_frac = the PMC opcode classes x the mixed-stream issue cycles "
+                            "measured by tools/valu_microbench.hip (profiles/valu_issue_costs.json: the upper end; "
+                            "issue_cost_pure_stream_bound prices every opcode as a stream of its own and can exceed 1); fp32_flop_frac = "
+                            "FP32 operations on active lanes / 157.3 TF/s; hbm_measured_frac = PMC bytes / kernel time / 8 TB/s"
+                            + ("; N > 1: counters of rank 0's own shard launch, taken before it joined the process group" if world > 1 else ""))
+            out["roofline"] = roof
         if census is not None:
             out["ranks_joined"] = dist.get_world_size()
             out["devices"] = census
@@ -604,11 +642,11 @@ def main():
             out["verify"] = verify_mode
         if final_only is not None:
             out["final_gather_only"] = final_only
-        if world == 1 and args.workload == "C3" and not args.force_dist:
+        if args.full and world == 1 and args.workload == "C3" and not args.force_dist:
             out["lens_extension"] = lens_extension_rate(b, torch, scene_name, w, h)
             if not args.no_other_configs:
                 out["other_configs"] = other_configs(b, torch, pmc_by_config=pmc_other)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene_name, w, h, args.cpu_budget)
             out["parity"] = parity_figure(b, torch, scene_name)
         print(json.dumps(out), flush=True)

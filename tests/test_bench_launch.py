@@ -1,14 +1,17 @@
 """bench.py's launcher logic, on CPU: `python bench.py --gpus N` typed from a bare shell must start one rank per GPU as a
 CHILD process (the reference's only parallelism, `chunks.into_par_iter()` tracer/mod.rs:190-197, becomes one process per
-GPU here), and the counter harness must be able to profile one rank's shard launch."""
+GPU here), and the counter harness must be able to profile one rank's shard launch.  On the GPU: a plain run prints the
+headline alone and its --dump-outputs frame is what the timed renders accumulated."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
+from helpers import gpu_scene
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
@@ -56,6 +59,42 @@ def test_under_a_launcher_the_environment_wins():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--help"], env=e, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=60)
     assert r.returncode == 0 and b"--print-launch" in r.stdout and b"--no-verify" in r.stdout
+
+
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=60)
+    assert r.returncode == 2 and b"--steps must be at least 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_timed_frame(tmp_path, bendy):
+    """Two plain runs with the same arguments: the same frame, bit for bit, equal to the warmup + timed renders done here;
+    nothing beyond the headline in the line (the rest is --full)."""
+    import torch
+    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    frames = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "C2", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(out)], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert not {"roofline", "lens_extension", "other_configs", "cpu_baseline", "parity"} & set(d)
+        assert sorted(os.listdir(out)) == ["frame.npy"]
+        frames.append(np.load(out / "frame.npy"))
+    assert frames[0].dtype == np.float32 and frames[0].shape == (512, 512, 4)
+    assert np.array_equal(frames[0], frames[1])
+    sc, cam = gpu_scene(bendy, "cornell2", 512, 512)
+    buf = bendy.Buffer.new(512, 512)
+    tr = bendy.Tracer.with_config(bendy.Config(chunks_x=8, chunks_y=4))
+    for i in range(4):
+        tr.render(sc, cam, bendy.RenderConfig.with_samples(16), buf, seed=0x5EED, sample_base=i * 16)
+    torch.cuda.synchronize()
+    assert np.array_equal(frames[0], buf.numpy())
 
 
 def test_pmc_harness_can_profile_one_ranks_shard():

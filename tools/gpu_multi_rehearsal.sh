@@ -7,10 +7,10 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r03}; mkdir -p $O
 unset WORLD_SIZE RANK LOCAL_RANK
 export MASTER_ADDR=127.0.0.1
-timeout -k 10 300 python bench.py --force-dist --backend rccl-abi --steps 5 --warmup 2 --no-cpu-baseline --verify > $O/bench_rccl_abi_world1.log 2>$O/bench_rccl_abi_world1.err; echo "rccl-abi world 1 rc=$?"; cut -c1-400 $O/bench_rccl_abi_world1.log
-timeout -k 10 300 python bench.py --force-dist --backend nccl --steps 5 --warmup 2 --no-cpu-baseline --verify > $O/bench_nccl_world1.log 2>&1; echo "nccl world 1 rc=$?"
+timeout -k 10 300 python bench.py --force-dist --backend rccl-abi --steps 5 --warmup 2 --full --no-cpu-baseline --verify > $O/bench_rccl_abi_world1.log 2>$O/bench_rccl_abi_world1.err; echo "rccl-abi world 1 rc=$?"; cut -c1-400 $O/bench_rccl_abi_world1.log
+timeout -k 10 300 python bench.py --force-dist --backend nccl --steps 5 --warmup 2 --full --no-cpu-baseline --verify > $O/bench_nccl_world1.log 2>&1; echo "nccl world 1 rc=$?"
 for cfg in "2 weak C3" "3 strong C3" "2 strong C2"; do set -- $cfg
-  timeout -k 10 500 python bench.py --gpus $1 --backend gloo --single-device --scaling $2 --workload $3 --steps 4 --warmup 1 --no-cpu-baseline > $O/bench_gloo$1_$2_$3.log 2>$O/bench_gloo$1_$2_$3.err; echo "gloo $cfg rc=$?"
+  timeout -k 10 500 python bench.py --gpus $1 --backend gloo --single-device --scaling $2 --workload $3 --steps 4 --warmup 1 --full --no-cpu-baseline > $O/bench_gloo$1_$2_$3.log 2>$O/bench_gloo$1_$2_$3.err; echo "gloo $cfg rc=$?"
   python3 - $O/bench_gloo$1_$2_$3.log <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")][-1]

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 TAG=$1; WL=$2
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmcq_$TAG
 mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-BENCH="python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --workload $WL"
+BENCH="python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --workload $WL"
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS --output-format csv -d $OUT/a -o pmc -- $BENCH > $OUT/a.log 2>&1
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d $OUT/b -o pmc -- $BENCH > $OUT/b.log 2>&1
 python3 - <<PY
