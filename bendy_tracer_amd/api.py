@@ -131,6 +131,11 @@ class _CTuning(C.Structure):  # include/bendy_hip.h `bt_tuning`
                 ("reserved", C.c_int32)]
 
 
+class _CDenoiseParams(C.Structure):  # include/bendy_hip.h `bt_denoise_params` (extension)
+    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("eps_albedo", C.c_float)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -143,7 +148,8 @@ EXPORTS = [
     "bt_shard_floats", "bt_render_shard_device", "bt_unshard_device", "bt_preview_device", "bt_preview",
     "bt_comm_unique_id", "bt_comm_init", "bt_comm_free", "bt_comm_rank", "bt_comm_world", "bt_allgather_shards_device",
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
-    "bt_scene_trim",
+    "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
+    "bt_denoise",
 ]
 
 
@@ -205,6 +211,13 @@ def _load():
     L.bt_scene_set_tuning.argtypes = [vp, C.POINTER(_CTuning)]
     L.bt_scene_get_tuning.argtypes = [vp, C.POINTER(_CTuning)]
     L.bt_scene_trim.argtypes = [vp]
+    L.bt_denoise_params_default.argtypes = [C.POINTER(_CDenoiseParams)]
+    L.bt_denoiser_new.restype = vp
+    L.bt_denoiser_free.argtypes = [vp]
+    L.bt_denoise_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32,
+                                    C.c_uint32, C.POINTER(_CDenoiseParams), vp]
+    L.bt_denoise.argtypes = [vp, fp, C.c_uint32, fp, C.c_uint32, fp, C.c_uint32, fp, C.c_uint32, fp, C.c_uint32, C.c_uint32,
+                             C.POINTER(_CDenoiseParams)]
     return L
 
 
@@ -514,6 +527,87 @@ class Comm:
         import torch
         _check(lib.bt_exchange_frame_device(self._h, shard.data_ptr(), gathered.data_ptr(), buffer.data.data_ptr(),
                                             buffer.width, buffer.height, torch.cuda.current_stream().cuda_stream))
+
+
+@dataclass
+class DenoiseParams:
+    """`bt_denoise_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Defaults = bt_denoise_params_default."""
+    levels: int = 2
+    sigma_color: float = 16.0
+    sigma_normal: float = 16.0
+    sigma_depth: float = 1.0
+    eps_albedo: float = 1e-3
+
+    def _c(self):
+        return _CDenoiseParams(int(self.levels), self.sigma_color, self.sigma_normal, self.sigma_depth, self.eps_albedo)
+
+
+class Denoiser:
+    """`bt_denoiser` (include/bendy_hip.h): EXTENSION, not in the reference -- the AOV-guided a-trous denoiser.  The handle
+    owns the scratch (48 B per pixel, grown on demand), so a caller that denoises every displayed frame keeps one."""
+
+    def __init__(self):
+        h = lib.bt_denoiser_new()
+        if not h:
+            raise BendyError(-1, "bt_denoiser_new failed")
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_denoiser_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def denoise(self, color: Buffer, albedo: Optional[Buffer] = None, normal: Optional[Buffer] = None,
+                depth: Optional[Buffer] = None, *, out: Optional[Buffer] = None, **params) -> Buffer:
+        """Filters `color` guided by the BT_OUTPUT_ALBEDO / _NORMAL / _DEPTH sums of the same frame (any of them may be
+        None), each divided by its own `.samples`.  Returns `out` (a new Buffer by default) holding the MEAN with
+        samples = 1 and the colour buffer's color_space, so `.preview()` works unchanged.  Keywords = DenoiseParams fields."""
+        p = DenoiseParams(**params)
+        bufs = [b for b in (albedo, normal, depth) if b is not None]
+        for b in bufs + ([out] if out is not None else []):
+            if (b.width, b.height) != (color.width, color.height):
+                raise BendyError(-1, f"buffer of {b.width}x{b.height} next to a {color.width}x{color.height} colour buffer")
+            if b.device != color.device or (color.device != "cpu" and b.data.device != color.data.device):
+                raise BendyError(-1, f"buffer on {b.device} next to a colour buffer on {color.device}")
+        if out is not None and any(out is b or out.data is b.data for b in [color] + bufs):
+            raise BendyError(-1, "out must not be one of the inputs: the inputs are running sums, out is a mean")
+        if out is None:
+            out = Buffer(color.width, color.height, color.color_space, device=color.device)
+        out.color_space = color.color_space
+
+        def arg(b):
+            if b is None:
+                return None, 0
+            if b.device == "cpu":
+                return b.data.ctypes.data_as(C.POINTER(C.c_float)), b.samples
+            return b.data.data_ptr(), b.samples
+
+        args = []
+        for b in (color, albedo, normal, depth):
+            args += list(arg(b))
+        cp = p._c()
+        if color.device == "cpu":
+            _check(lib.bt_denoise(self._h, *args, arg(out)[0], color.width, color.height, C.byref(cp)))
+        else:
+            import torch
+            _check(lib.bt_denoise_device(self._h, *args, out.data.data_ptr(), color.width, color.height, C.byref(cp),
+                                         torch.cuda.current_stream().cuda_stream))
+        out.samples = 1
+        return out
+
+
+_default_denoiser = None
+
+
+def denoise(color: Buffer, albedo: Optional[Buffer] = None, normal: Optional[Buffer] = None, depth: Optional[Buffer] = None,
+            *, out: Optional[Buffer] = None, **params) -> Buffer:
+    """EXTENSION, not in the reference: Denoiser.denoise on a process-wide handle (see there)."""
+    global _default_denoiser
+    if _default_denoiser is None:
+        _default_denoiser = Denoiser()
+    return _default_denoiser.denoise(color, albedo, normal, depth, out=out, **params)
 
 
 def write_png(path, rgba8):

@@ -8,7 +8,10 @@
 // the frame in HBM, prints what the window title would show (main.rs:352-388) and then does what
 // Ctrl+P does (preview -> PNG, main.rs:275-298) and, with --save-scene, what Ctrl+K does
 // (pretty JSON, gzip for .gz, main.rs:299-313).  Extra flags: --seed, --save-scene, --device, --quiet, and
-// --lens x,y,z,rs,step,radius[,max_steps] for the gravitational-lens EXTENSION (not in the reference; bt_lens).
+// --lens x,y,z,rs,step,radius[,max_steps] for the gravitational-lens EXTENSION (not in the reference; bt_lens), and
+// --denoise [--denoise-guide-samples N] for the denoiser EXTENSION (not in the reference; bt_denoiser): after the loop the
+// albedo, normal and depth AOVs are rendered with N x subsample^2 rays per pixel (same seed) and the screenshot is the
+// denoised mean.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -78,6 +81,8 @@ struct Args {
                                                          // harness for bench.py --gpus N; no screenshot, the shard is tile-major)
     bool has_lens = false;
     bt_lens lens{};
+    bool denoise = false;
+    unsigned denoise_guide_samples = 4;
 };
 
 void usage() {
@@ -86,7 +91,8 @@ void usage() {
                  "       [--subsample 2] [--screenshot screenshots/render.png] [--scene scene.json]\n"
                  "       [--seed N] [--save-scene PATH] [--device N] [--quiet]\n"
                  "       [--samples-per-call 1] [--no-screenshot] [--stats-json PATH] [--shard rank,world]   (measurement harness)\n"
-                 "       [--lens x,y,z,rs,step,radius[,max_steps]]   (extension: not in the reference)\n");
+                 "       [--lens x,y,z,rs,step,radius[,max_steps]]   (extension: not in the reference)\n"
+                 "       [--denoise] [--denoise-guide-samples 4]   (extension: not in the reference; --output full only)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -131,11 +137,16 @@ Args parse(int argc, char **argv) {
             a.lens.max_steps = (uint32_t)f[6];
             a.has_lens = true;
         }
+        else if (k == "--denoise") a.denoise = true;
+        else if (k == "--denoise-guide-samples") a.denoise_guide_samples = (unsigned)std::strtoul(val().c_str(), nullptr, 10);
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
     if (a.output.empty()) { usage(); die("the following required arguments were not provided: --output <OUTPUT>"); }
     if (a.width == 0 || a.height == 0) die("width and height must be positive");
+    if (a.denoise && a.output != "full") die("--denoise needs --output full");
+    if (a.denoise && a.shard_world > 1) die("--denoise does not apply to a --shard run");
+    if (a.denoise && a.denoise_guide_samples == 0) die("--denoise-guide-samples must be positive");
     return a;
 }
 
@@ -263,8 +274,38 @@ int main(int argc, char **argv) {
             }
         }
     }
+    // --denoise (extension): the guides of the same frame into fresh buffers, then the screenshot shows the denoised mean
+    float *d_shown = d_frame;
+    unsigned shown_samples = buffer_samples ? buffer_samples : 1;
+    float *d_guides[4] = {nullptr, nullptr, nullptr, nullptr};          // albedo, normal, depth, denoised mean
+    if (args.denoise && !args.no_screenshot) {
+        for (int g = 0; g < 4; ++g) {
+            hip_check(hipMalloc((void **)&d_guides[g], n_px * 16), "hipMalloc");
+            hip_check(hipMemcpy(d_guides[g], init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        const int aov[3] = {BT_OUTPUT_ALBEDO, BT_OUTPUT_NORMAL, BT_OUTPUT_DEPTH};
+        bt_config gcfg = cfg;
+        bt_render_config grc = rc;
+        grc.samples = args.denoise_guide_samples;
+        grc.sample_base = 0;
+        for (int g = 0; g < 3; ++g) {
+            gcfg.output = aov[g];
+            check(bt_render_device(scene, camera, &gcfg, &grc, d_guides[g], args.width, args.height, args.seed, nullptr),
+                  "bt_render_device (denoise guide)");
+        }
+        const uint32_t gs = args.denoise_guide_samples * nn;
+        bt_denoiser *dn = bt_denoiser_new();
+        check(bt_denoise_device(dn, d_frame, shown_samples, d_guides[0], gs, d_guides[1], gs, d_guides[2], gs, d_guides[3],
+                                args.width, args.height, nullptr, nullptr),
+              "bt_denoise_device");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bt_denoiser_free(dn);
+        d_shown = d_guides[3];
+        shown_samples = 1;                                  // the denoised buffer holds a mean
+        std::fprintf(stderr, "denoised with guides of %u samples\n", gs);
+    }
     if (!args.no_screenshot) {
-        check(bt_preview_device(d_frame, d_rgba8, args.width, args.height, buffer_samples ? buffer_samples : 1, color_space, nullptr),
+        check(bt_preview_device(d_shown, d_rgba8, args.width, args.height, shown_samples, color_space, nullptr),
               "bt_preview_device");
         std::vector<uint8_t> rgba8(n_px * 4);
         hip_check(hipMemcpy(rgba8.data(), d_rgba8, n_px * 4, hipMemcpyDeviceToHost), "hipMemcpy");
@@ -280,6 +321,8 @@ int main(int argc, char **argv) {
 
     (void)hipFree(d_frame);
     (void)hipFree(d_rgba8);
+    for (float *g : d_guides)
+        if (g) (void)hipFree(g);
     bt_scene_free(scene);
     return 0;
 }

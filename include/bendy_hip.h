@@ -220,6 +220,39 @@ int bt_preview_device(const float *rgba_device, uint8_t *rgba8_device, uint32_t 
 int bt_preview(const float *rgba_host, uint8_t *rgba8_host, uint32_t width, uint32_t height, uint32_t samples,
                int32_t color_space);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: AOV-guided a-trous denoiser ------------------------------
+ * bendy-tracer v1 has no denoiser.  This one is off unless called, makes no parity claim and changes no render.
+ * Edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) on the albedo-demodulated colour (as in SVGF),
+ * guided by the BT_OUTPUT_ALBEDO / _NORMAL / _DEPTH sums of the same frame.  Inputs are RGBA32F running sums, each
+ * with its own sample count; albedo, normal and depth may be NULL (that guide's weight is then 1).  `out` receives
+ * the MEAN (preview it with samples = 1): out.rgb = filtered colour, out.a = the colour buffer's alpha;
+ * levels == 0 writes the plain mean.  `out` must not be one of the inputs.  Invalid arguments are rejected before
+ * the device is touched (BT_ERR_INVALID_ARG); a valid call without a device returns BT_ERR_DEVICE. */
+typedef struct {
+    uint32_t levels;           /* a-trous levels (steps 1, 2, 4, ...), 0 .. 10 */
+    float sigma_color;         /* > 0: colour edge stop, exp(-|e_p - e_q|^2 4^i / sigma_color^2) at level i */
+    float sigma_normal;        /* >= 0: normal edge stop, max(0, n_p . n_q)^sigma_normal */
+    float sigma_depth;         /* > 0: depth edge stop, relative to the centre's depth */
+    float eps_albedo;          /* >= 0: albedo channels <= eps_albedo are not demodulated */
+} bt_denoise_params;
+typedef struct bt_denoiser bt_denoiser;   /* owns the scratch (48 B per pixel); grows on demand; one stream at a time */
+void bt_denoise_params_default(bt_denoise_params *out);
+bt_denoiser *bt_denoiser_new(void);
+void bt_denoiser_free(bt_denoiser *d);
+/* Device-resident buffers (w * h * 4 floats each); `stream` is a hipStream_t (NULL = default stream).  Enqueues
+ * levels + 1 kernels and returns without synchronising.  params == NULL: bt_denoise_params_default. */
+int bt_denoise_device(bt_denoiser *d, const float *color, uint32_t color_samples,
+                      const float *albedo, uint32_t albedo_samples,
+                      const float *normal, uint32_t normal_samples,
+                      const float *depth, uint32_t depth_samples,
+                      float *out, uint32_t width, uint32_t height, const bt_denoise_params *params, void *stream);
+/* Host buffers: copied through the device like bt_render (device staging kept on the handle); blocks until `out` is written. */
+int bt_denoise(bt_denoiser *d, const float *color, uint32_t color_samples,
+               const float *albedo, uint32_t albedo_samples,
+               const float *normal, uint32_t normal_samples,
+               const float *depth, uint32_t depth_samples,
+               float *out, uint32_t width, uint32_t height, const bt_denoise_params *params);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);
