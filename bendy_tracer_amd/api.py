@@ -149,7 +149,7 @@ EXPORTS = [
     "bt_comm_unique_id", "bt_comm_init", "bt_comm_free", "bt_comm_rank", "bt_comm_world", "bt_allgather_shards_device",
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
-    "bt_denoise",
+    "bt_denoise", "bt_debug_primary_mask",
 ]
 
 
@@ -187,6 +187,8 @@ def _load():
     L.bt_scene_object_count.argtypes = [vp]
     L.bt_scene_data_count.argtypes = [vp]
     L.bt_scene_export_prims.argtypes = [vp, fp, C.c_int]
+    L.bt_debug_primary_mask.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32]
     L.bt_render.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), fp, C.c_uint32,
                             C.c_uint32, C.c_uint64]
     L.bt_render_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp, C.c_uint32,
@@ -475,6 +477,17 @@ class Tracer:
         if rc == Status.InProgress:
             buffer.inc_samples(config.samples * nn)  # mod.rs:199
         return Status(rc)
+
+    def primary_masks(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1):
+        """bt_debug_primary_mask (tests): per block of a launch with `slices` blocks per tile, in launch order, the
+        sphere rows a primary ray of the block may hit (uint64 bit masks)."""
+        c, r = _c_configs(self.config, config, 0)
+        n = _check(lib.bt_debug_primary_mask(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world,
+                                             None, 0))
+        out = np.zeros(n, dtype=np.uint64)
+        _check(lib.bt_debug_primary_mask(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world,
+                                         out.ctypes.data_as(C.POINTER(C.c_uint64)), n))
+        return out
 
     # ---- multi-GPU tile sharding (DESIGN.md "Multi-GPU") ----
     def render_shard(self, scene: Scene, camera: int, config: RenderConfig, shard, width, height, rank, world,

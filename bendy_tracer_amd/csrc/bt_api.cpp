@@ -21,6 +21,7 @@ extern "C" hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned g
 extern "C" hipError_t bt_launch_unshard(const float *gathered, float *frame, uint32_t width, uint32_t height,
                                         uint32_t tiles_x, uint32_t tiles_y, uint32_t world, uint32_t tiles_per_rank,
                                         hipStream_t stream);
+extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows, uint32_t n_blocks, uint64_t *out);
 extern "C" hipError_t bt_launch_preview(const float *rgba, uint8_t *out, uint32_t n, uint32_t samples, int color_space,
                                         hipStream_t stream);
 
@@ -141,6 +142,17 @@ int ensure_flat(bt_scene *s) {
     return 0;
 }
 
+// BtSphereRow table of a sphere-only scene (bt_types.h), empty when any row is not a sphere
+std::vector<BtSphereRow> sphere_rows_of(const std::vector<BtPrim> &pr) {
+    std::vector<BtSphereRow> rows;
+    bool spheres_only = true;
+    for (const BtPrim &R : pr) spheres_only = spheres_only && (R.kind & BT_PRIM_SHAPE_MASK) == BT_PRIM_SPHERE;
+    if (spheres_only)
+        for (const BtPrim &R : pr) rows.push_back(BtSphereRow{R.c.x, R.c.y, R.c.z, R.radius * R.radius});
+    if (rows.size() & 1) rows.push_back(rows.back());           // (never visited: keeps an x8 load of the last pair inside the table)
+    return rows;
+}
+
 int ensure_device(bt_scene *s) {
     int rc = ensure_flat(s);
     if (rc) return rc;
@@ -178,11 +190,7 @@ int ensure_device(bt_scene *s) {
                 pairs.push_back(q);
             }
         BT_HIP(s->d_sphere_pairs.upload(pairs));
-        std::vector<BtSphereRow> rows;
-        if (spheres_only)
-            for (const BtPrim &R : pr) rows.push_back(BtSphereRow{R.c.x, R.c.y, R.c.z, R.radius * R.radius});
-        if (rows.size() & 1) rows.push_back(rows.back());           // (never visited: keeps an x8 load of the last pair inside the table)
-        BT_HIP(s->d_sphere_rows.upload(rows));
+        BT_HIP(s->d_sphere_rows.upload(sphere_rows_of(pr)));
     }
     BT_HIP(s->d_density.upload(s->flat.density));
     BT_HIP(s->d_aan_rows.upload(s->flat.aan_rows));
@@ -773,6 +781,34 @@ int bt_scene_export_prims(const bt_scene *scene, float *out, int cap) {
     const int total = (int)(s->flat.prims.size() * words);
     if (out && cap > 0) std::memcpy(out, s->flat.prims.data(), sizeof(float) * (size_t)std::min(cap, total));
     return total;
+}
+
+int bt_debug_primary_mask(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                          uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint64_t *masks,
+                          uint32_t cap) {
+    if (!scene || !config || !render) return set_error(BT_ERR_INVALID_ARG, "null argument");
+    if (slices == 0 || slices > 32 || (slices & (slices - 1)) != 0) return set_error(BT_ERR_INVALID_ARG, "slices must be 1, 2, 4, ..., 32");
+    if (world == 0 || rank >= world) return set_error(BT_ERR_INVALID_ARG, "rank/world out of range");
+    int rc = ensure_flat(scene);
+    if (rc) return rc;
+    BtLaunch P;
+    int output = 0;
+    rc = fill_launch(scene, camera_ref, config, render, width, height, 0, P, output);
+    if (rc) return rc;
+    P.rank = rank;
+    P.world = world;
+    P.sharded = world > 1 ? 1 : 0;
+    P.slices = (int32_t)slices;
+    const uint32_t n_tiles = P.tiles_x * P.tiles_y, grid = (n_tiles + world - 1) / world;
+    const uint64_t n_blocks = (uint64_t)grid * slices;
+    if (n_blocks > 0x7fffffffu) return set_error(BT_ERR_INVALID_ARG, "too many blocks");
+    const std::vector<BtSphereRow> rows = sphere_rows_of(scene->flat.prims);
+    if (masks && cap > 0) {
+        std::vector<uint64_t> all((size_t)n_blocks, ~0ull);
+        if (P.any_rects == 0 && P.any_volumes == 0) bt_primary_masks_host(&P, rows.data(), (uint32_t)n_blocks, all.data());
+        std::memcpy(masks, all.data(), sizeof(uint64_t) * (size_t)std::min<uint64_t>(cap, n_blocks));
+    }
+    return (int)n_blocks;
 }
 
 int bt_render_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,

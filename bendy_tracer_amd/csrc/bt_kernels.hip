@@ -37,6 +37,7 @@
 // change lanes -- a "march stack" for paths that enter a volume (profiles/r04d) and end-of-block compaction (profiles/r04c,
 // r04e, r04f).
 #include "bt_device.hpp"
+#include "bt_cull.hpp"
 
 #define BT_SUM_BATCH 8             // parked values a lane of the summing wave has in flight (16: no difference, profiles/r04k)
 
@@ -79,7 +80,9 @@ BT_DEV uint32_t lanes_below(unsigned long long m) {
 // b mod NS of the launch's tile b / NS.  The tile (a division by tiles_x: umulhi + one fix-up step) and the block's corner
 // inside it depend on the block alone: computed once per block (wave-uniform: scalar), not once per work item.
 struct BlockGeom { uint32_t NS, LOG_NS, pxb, LOG_PXB, LBW, WMASK; };
-BT_DEV BlockGeom block_geom(const BtLaunch &P) {
+// (block_geom, block_ref and block_extent also run on the host: bt_debug_primary_mask)
+#define BT_HDF static __host__ __device__ __forceinline__
+BT_HDF BlockGeom block_geom(const BtLaunch &P) {
     BlockGeom g;
     g.NS = (uint32_t)P.slices;
     g.LOG_NS = (uint32_t)__builtin_ctz(g.NS);
@@ -90,10 +93,14 @@ BT_DEV BlockGeom block_geom(const BtLaunch &P) {
     return g;
 }
 struct BlockRef { uint32_t px0, py0, tile_ok, slot; };
-BT_DEV BlockRef block_ref(const BtLaunch &P, const BlockGeom &g, uint32_t b) {      // b: block in launch order
+BT_HDF BlockRef block_ref(const BtLaunch &P, const BlockGeom &g, uint32_t b) {      // b: block in launch order
     const uint32_t slot = b >> g.LOG_NS, sub = b & (g.NS - 1u);
     const uint32_t tile = P.sharded ? (slot * P.world + P.rank) : slot;
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t ty = __umulhi(tile, P.tiles_x_magic), tx = tile - ty * P.tiles_x;      // tile / tiles_x, exact after the fix-up
+#else
+    uint32_t ty = (uint32_t)(((uint64_t)tile * P.tiles_x_magic) >> 32), tx = tile - ty * P.tiles_x;
+#endif
     if (tx >= P.tiles_x) { ty += 1u; tx -= P.tiles_x; }
     // corner of block `sub` inside the tile: 128 pixels = the quadrant row `sub`, 64 = quadrant `sub`, below that blocks
     // of 8x4 / 4x4 / 4x2 pixels numbered row-major
@@ -111,6 +118,13 @@ BT_DEV BlockRef block_ref(const BtLaunch &P, const BlockGeom &g, uint32_t b) {  
     r.tile_ok = ty < P.tiles_y ? 1u : 0u;
     r.slot = slot;
     return r;
+}
+// the block's pixels inside the frame: the rectangle [px0, px0 + nx) x [py0, py0 + ny) (nx = 0 or ny = 0: none).  A block is
+// 16 pixels wide when it holds whole rows of quadrants (pxb >= 128), else 2^LBW; pxb >> log2(width) rows high.
+BT_HDF void block_extent(const BtLaunch &P, const BlockGeom &g, const BlockRef &B, uint32_t &nx, uint32_t &ny) {
+    const uint32_t lw = g.pxb >= 128 ? 4u : g.LBW, bw = 1u << lw, bh = g.pxb >> lw;
+    nx = B.tile_ok && B.px0 < P.width ? (P.width - B.px0 < bw ? P.width - B.px0 : bw) : 0u;
+    ny = B.tile_ok && B.py0 < P.height ? (P.height - B.py0 < bh ? P.height - B.py0 : bh) : 0u;
 }
 // pixel q of a block: quadrants 1 .. 3 of a 128- or 256-pixel block sit to the right of / below quadrant 0
 struct PixelRef { uint32_t px, py; bool in_frame; };
@@ -402,6 +416,55 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
     unsigned long long ls_acc[9] = {};
     const unsigned long long ls_all = __ballot(true);
 #endif
+    // ---- a block whose camera rays provably reach no sphere (sphere-only builds without volumes) ----
+    // Every sample of such a block is one segment that misses: its value is sample_root's with the camera's beta and L.
+    // The workgroup adds that value T times to each pixel's running sum -- the additions sum_block() would perform on the
+    // parked values, in the same order -- and traces nothing.  Every wave decides the same (same inputs, same
+    // operations): no barrier.  The Normal output's miss value depends on the direction and is not shortcut.
+    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2;
+    if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE)
+        uint32_t nx = 0, ny = 0;
+        block_extent(P, G, B_own, nx, ny);
+        bool reach = false;                        // may any primary ray of the block hit any sphere row?
+        if (nx != 0u && ny != 0u && P.n_prims > 0) {
+            if (P.n_prims > 64) {
+                reach = true;
+            } else {                               // lanes = sphere rows, one ballot
+                const btcull::Cone K = btcull::primary_cone(P, B_own.px0, B_own.py0, nx, ny);
+                bool mine = false;
+                if ((int)lane < P.n_prims) {
+                    const BtSphereRow R = P.sphere_rows[lane];
+                    mine = btcull::may_hit(K, R.cx, R.cy, R.cz, R.r2);
+                }
+                reach = __ballot(mine) != 0ull;
+            }
+        }
+        if (!reach) {
+            V3 value;
+            if (OUTPUT == 0) {
+                value = mk(0, 0, 0) + mk(1, 1, 1) * mk(P.root_color);      // L = L + beta * root_color, fresh L and beta
+            } else if (OUTPUT == 1) {
+                value = mk(P.root_albedo);
+            } else {
+                const float fd = P.root_has_albedo ? P.clip_max : __builtin_inff();
+                float depth = (fd - P.clip_min) / (P.clip_max - P.clip_min);
+                depth = fminf(fmaxf(depth, 0.0f), 1.0f);
+                value = mk(depth, depth, depth);
+            }
+            for (uint32_t q = threadIdx.x; q < pxb; q += blockDim.x) {
+                const PixelRef r = pixel_of(P, G, B_own, q);
+                if (!r.in_frame) continue;
+                float *o = out_of(P, B_own, r);
+                V3 sum = mk(o[0], o[1], o[2]);
+                for (uint32_t k = 0; k < T; ++k) sum = sum + value;
+                o[0] = sum.x;
+                o[1] = sum.y;
+                o[2] = sum.z;
+            }
+            if (P.counters && threadIdx.x == 0 && nx * ny != 0u) atomicAdd(&P.counters[0], (unsigned long long)(nx * ny) * T);
+            goto block_done;
+        }
+    }
     for (;;) {
         do {                                              // (`continue` below = on to the latch at the end of the iteration)
         if (compacting && dry_lane && pending) continue;  // the queue is empty and this lane has no path: nothing to do
@@ -881,6 +944,7 @@ queue_empty:;
             sum_block(P, G, blockIdx.x, T, park(), lane);
         }
     }
+block_done:;
     if (P.counters) {
         if (LENS) {
             unsigned long long ls = wave_sum(lens_steps);
@@ -976,6 +1040,27 @@ __global__ __launch_bounds__(256) void bt_preview_kernel(const float4 *rgba, uin
 }
 
 // ---- host-side launchers (called from bt_api.cpp) ---------------------------------------------
+// bt_debug_primary_mask: the masks the sphere-only build computes in its prologue, one per block of the launch `P` describes
+// (blocks in launch order), bit i = sphere row i may be hit; computed here on the host by the same code (bt_cull.hpp).
+extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows, uint32_t n_blocks, uint64_t *out) {
+    const BlockGeom G = block_geom(*P);
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        const BlockRef B = block_ref(*P, G, b);
+        uint32_t nx = 0, ny = 0;
+        block_extent(*P, G, B, nx, ny);
+        uint64_t m = 0;
+        if (nx != 0u && ny != 0u && P->n_prims > 0) {
+            if (P->n_prims > 64) {
+                m = ~0ull;
+            } else {
+                const btcull::Cone K = btcull::primary_cone(*P, B.px0, B.py0, nx, ny);
+                for (int i = 0; i < P->n_prims; ++i)
+                    if (btcull::may_hit(K, rows[i].cx, rows[i].cy, rows[i].cz, rows[i].r2)) m |= 1ull << i;
+            }
+        }
+        out[b] = m;
+    }
+}
 extern "C" hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned grid, size_t lds_bytes,
                                        hipStream_t stream) {
     // grid = tiles to render; a tile is P->slices workgroups (see the mapping in the kernel)

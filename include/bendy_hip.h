@@ -157,6 +157,14 @@ int bt_scene_data_count(const bt_scene *scene);
 /* Flattened primitive table as uploaded to the GPU, for loader cross-checks:
  * writes up to `cap` floats, returns the number available. */
 int bt_scene_export_prims(const bt_scene *scene, float *out, int cap);
+/* For tests: the per-block sphere masks of the sphere-only build without volumes, computed on the host
+ * by the kernel's own code.  Blocks of a launch with `slices` (1, 2, 4, ..., 32) blocks per 16x16 tile, in launch order:
+ * tile-major over the frame, or over rank `rank`'s tiles when world > 1.  Bit i set = sphere row i may be hit by a primary
+ * ray of the block; a block with no bit set traces nothing.  Writes up to `cap` masks (masks may be NULL) and returns the
+ * number of blocks; every bit is set for scenes that do not run that build. */
+int bt_debug_primary_mask(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                          uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint64_t *masks,
+                          uint32_t cap);
 
 /* --- Tracer::render (tracer/mod.rs:179-202) ----------------------------------------
  * Adds `samples * n^2` radiance samples per pixel into the RGB channels of `rgba`
