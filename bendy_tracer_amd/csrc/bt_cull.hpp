@@ -104,10 +104,14 @@ BT_HD Cone primary_cone(const BtLaunch &P, uint32_t px0, uint32_t py0, uint32_t 
     alpha += 2e-4;
     double rho = 0.0;
     if (P.has_focus) {
-        // origin cam_t + M (disk * aperture), |disk| <= (|disk_x| + |disk_y|) * one_scale; direction f d1 - offset with
-        // f = focus / |d_cam.z| >= focus: it leans away from d1 by at most asin(rho / focus) <= r + r^3 (r <= 1/2)
-        const double dl = dsqrt(ddot(d3(P.disk_x), d3(P.disk_x))) + dsqrt(ddot(d3(P.disk_y), d3(P.disk_y)));
-        rho = s * dabs((double)P.aperture) * dl * dabs((double)P.one_scale) * (1.0 + 1e-4);
+        // origin cam_t + M (aperture (disk_x cs + disk_y sn) r2) with r2 <= one_scale and cs^2 + sn^2 <= 1 + 1e-6:
+        // |disk_x cs + disk_y sn|^2 <= (cs^2 + sn^2) lmax, lmax <= max(|disk_x|^2, |disk_y|^2) + |disk_x . disk_y| the
+        // larger eigenvalue of their Gram matrix (orthonormal disk_x, disk_y: lmax = 1).  The 1e-4 covers that 1e-6, the
+        // float products and the matrix's 1e-5.  Direction f d1 - offset with f = focus / |d_cam.z| >= focus: it leans
+        // away from d1 by at most asin(rho / focus) <= r + r^3 (r <= 1/2)
+        const D3 dx = d3(P.disk_x), dy = d3(P.disk_y);
+        const double lmax = dmax(ddot(dx, dx), ddot(dy, dy)) + dabs(ddot(dx, dy));
+        rho = s * dabs((double)P.aperture) * dsqrt(lmax) * dabs((double)P.one_scale) * (1.0 + 1e-4);
         const double f_lo = (double)P.focus * (1.0 - 1e-5);
         if (!(f_lo > 0.0)) return K;
         const double r = rho / f_lo;
