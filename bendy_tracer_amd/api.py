@@ -149,7 +149,7 @@ EXPORTS = [
     "bt_comm_unique_id", "bt_comm_init", "bt_comm_free", "bt_comm_rank", "bt_comm_world", "bt_allgather_shards_device",
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
-    "bt_denoise", "bt_debug_primary_mask",
+    "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_set_object",
 ]
 
 
@@ -189,6 +189,10 @@ def _load():
     L.bt_scene_export_prims.argtypes = [vp, fp, C.c_int]
     L.bt_debug_primary_mask.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32]
+    L.bt_debug_set_object.argtypes = [vp, C.c_uint64, fp, C.c_float]
+    L.bt_debug_block_masks_device.argtypes = L.bt_debug_primary_mask.argtypes
+    L.bt_debug_mask_key.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32]
     L.bt_render.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), fp, C.c_uint32,
                             C.c_uint32, C.c_uint64]
     L.bt_render_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp, C.c_uint32,
@@ -298,6 +302,11 @@ class Scene:
     def set_camera_aspect(self, camera_ref, aspect_ratio):
         """main.rs:218-223."""
         _check(lib.bt_scene_set_camera_aspect(self._h, camera_ref, aspect_ratio))
+
+    def debug_set_object(self, object_ref, translation=None, radius=0.0):
+        """bt_debug_set_object (tests): move an object / resize a sphere in place on this handle."""
+        t = None if translation is None else (C.c_float * 3)(*[float(v) for v in translation])
+        _check(lib.bt_debug_set_object(self._h, object_ref, t, float(radius)))
 
     def set_lens(self, centre, rs, step, radius, max_steps=4096):
         """EXTENSION, not in the reference (include/bendy_hip.h `bt_lens`): bend rays around a point mass."""
@@ -488,6 +497,24 @@ class Tracer:
         _check(lib.bt_debug_primary_mask(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world,
                                          out.ctypes.data_as(C.POINTER(C.c_uint64)), n))
         return out
+
+    def block_masks_device(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1):
+        """bt_debug_block_masks_device (tests): the same masks, written by bt_block_mask_kernel on the GPU."""
+        c, r = _c_configs(self.config, config, 0)
+        n = _check(lib.bt_debug_block_masks_device(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank,
+                                                   world, None, 0))
+        out = np.zeros(n, dtype=np.uint64)
+        _check(lib.bt_debug_block_masks_device(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world,
+                                               out.ctypes.data_as(C.POINTER(C.c_uint64)), n))
+        return out
+
+    def mask_key(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1) -> bytes:
+        """bt_debug_mask_key (tests): the key under which the handle would keep these masks between renders."""
+        c, r = _c_configs(self.config, config, 0)
+        n = _check(lib.bt_debug_mask_key(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world, None, 0))
+        out = (C.c_uint8 * n)()
+        _check(lib.bt_debug_mask_key(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world, out, n))
+        return bytes(out)
 
     # ---- multi-GPU tile sharding (DESIGN.md "Multi-GPU") ----
     def render_shard(self, scene: Scene, camera: int, config: RenderConfig, shard, width, height, rank, world,

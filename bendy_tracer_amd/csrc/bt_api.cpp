@@ -14,6 +14,7 @@
 #include "../../include/bendy_hip.h"
 #include "bt_scene.hpp"
 #include "bt_types.h"
+#include "bt_cull.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 
@@ -22,6 +23,9 @@ extern "C" hipError_t bt_launch_unshard(const float *gathered, float *frame, uin
                                         uint32_t tiles_x, uint32_t tiles_y, uint32_t world, uint32_t tiles_per_rank,
                                         hipStream_t stream);
 extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows, uint32_t n_blocks, uint64_t *out);
+extern "C" int bt_launch_reads_masks(const BtLaunch *P, int output);
+extern "C" int bt_mask_cache_enabled(void);
+extern "C" hipError_t bt_launch_block_masks(const BtLaunch *P, uint32_t n_blocks, uint64_t *masks, hipStream_t stream);
 extern "C" hipError_t bt_launch_preview(const float *rgba, uint8_t *out, uint32_t n, uint32_t samples, int color_space,
                                         hipStream_t stream);
 
@@ -92,6 +96,12 @@ struct bt_scene {
     float *d_scratch = nullptr;    // parked sample values of sliced renders
     size_t scratch_bytes = 0;
     uint32_t scratch_small_streak = 0;   // consecutive renders that needed less than a quarter of the scratch held
+    // per-block sphere masks of the last launch that read them (bt_cull.hpp block_mask): grow-only, reused as long as the key
+    // -- everything the masks depend on -- stays what it was (a progressive sequence, the launches of one deep render)
+    uint64_t *d_block_masks = nullptr;
+    size_t block_masks_cap = 0;    // masks the buffer holds room for
+    btcull::MaskKey masks_for{};   // valid = 0: none
+    uint64_t rows_generation = 0;  // bumped wherever d_sphere_rows is uploaded
     float *d_host_frame = nullptr; // device copy of the caller's host buffer (bt_render), kept between calls
     size_t host_frame_bytes = 0;
     int n_cu = 0;                  // hipDeviceProp_t::multiProcessorCount of `device`
@@ -108,11 +118,15 @@ struct bt_scene {
         if (d_counters) (void)hipFree(d_counters);
         if (d_scratch) (void)hipFree(d_scratch);
         if (d_host_frame) (void)hipFree(d_host_frame);
+        if (d_block_masks) (void)hipFree(d_block_masks);
         if (ev_start) (void)hipEventDestroy(ev_start);
         if (ev_stop) (void)hipEventDestroy(ev_stop);
         d_counters = nullptr;
         d_scratch = nullptr;
         d_host_frame = nullptr;
+        d_block_masks = nullptr;
+        block_masks_cap = 0;
+        masks_for = btcull::MaskKey{};
         scratch_bytes = host_frame_bytes = 0;
         scratch_small_streak = 0;
         ev_start = ev_stop = nullptr;
@@ -139,6 +153,7 @@ int ensure_flat(bt_scene *s) {
     }
     s->flat_valid = true;
     s->device_valid = false;
+    s->rows_generation += 1;                       // new rows (part of the block masks' key); the upload bumps it again
     return 0;
 }
 
@@ -191,6 +206,7 @@ int ensure_device(bt_scene *s) {
             }
         BT_HIP(s->d_sphere_pairs.upload(pairs));
         BT_HIP(s->d_sphere_rows.upload(sphere_rows_of(pr)));
+        s->rows_generation += 1;                   // (part of the block masks' key)
     }
     BT_HIP(s->d_density.upload(s->flat.density));
     BT_HIP(s->d_aan_rows.upload(s->flat.aan_rows));
@@ -564,6 +580,31 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
     s->render_seq += 1;
     P.counters = s->d_counters + (size_t)s->last_slot * 16;
     BT_HIP(hipEventRecord(s->ev_start, stream));
+    P.block_masks = nullptr;
+    if (bt_launch_reads_masks(&P, output)) {
+        // One mask per block, the same for every launch of this render (blocks and slices do not change with the sample
+        // range) and for every later render with the same key; computed on this stream, inside the timed region.
+        const uint32_t n_blocks = grid * (uint32_t)P.slices;
+        btcull::MaskKey key;
+        btcull::mask_key(key, P, n_blocks, s->rows_generation, (const void *)stream);
+        if (!bt_mask_cache_enabled() || std::memcmp(&key, &s->masks_for, sizeof key) != 0) {
+            if (s->block_masks_cap < n_blocks) {
+                if (s->d_block_masks) {
+                    BT_HIP(hipDeviceSynchronize());    // earlier launches, on whichever stream, may still read the old buffer
+                    (void)hipFree(s->d_block_masks);
+                }
+                s->d_block_masks = nullptr;
+                s->block_masks_cap = 0;
+                s->masks_for = btcull::MaskKey{};
+                BT_HIP(hipMalloc((void **)&s->d_block_masks, sizeof(uint64_t) * (size_t)n_blocks));
+                s->block_masks_cap = n_blocks;
+            }
+            s->masks_for = btcull::MaskKey{};          // (stays invalid if the launch fails)
+            BT_HIP(bt_launch_block_masks(&P, n_blocks, s->d_block_masks, stream));
+            s->masks_for = key;
+        }
+        P.block_masks = s->d_block_masks;
+    }
     {
         const uint32_t all = (uint32_t)P.samples, base = P.sample_base;
         for (uint32_t done = 0; done < all; done += chunk) {
@@ -783,15 +824,25 @@ int bt_scene_export_prims(const bt_scene *scene, float *out, int cap) {
     return total;
 }
 
-int bt_debug_primary_mask(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
-                          uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint64_t *masks,
-                          uint32_t cap) {
+int bt_debug_set_object(bt_scene *scene, uint64_t object_ref, const float *translation, float radius) {
+    if (!scene) return set_error(BT_ERR_INVALID_ARG, "null scene");
+    const int i = scene->scene.object_index(object_ref);
+    if (i < 0) return set_error(BT_ERR_INVALID_REF, "invalid object ref " + std::to_string(object_ref));
+    bt::Object &o = scene->scene.objects[i];
+    if (translation) { o.world.t.x = translation[0]; o.world.t.y = translation[1]; o.world.t.z = translation[2]; }
+    if (radius > 0.0f && o.kind == bt::OBJ_SPHERE) o.radius = radius;
+    scene->flat_valid = false;                            // the tables are flattened and uploaded again by the next render
+    return 0;
+}
+
+// the launch the bt_debug_* mask entry points describe: fill_launch + shard and block shape; returns the number of blocks
+static int debug_mask_launch(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                             uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, BtLaunch &P) {
     if (!scene || !config || !render) return set_error(BT_ERR_INVALID_ARG, "null argument");
     if (slices == 0 || slices > 32 || (slices & (slices - 1)) != 0) return set_error(BT_ERR_INVALID_ARG, "slices must be 1, 2, 4, ..., 32");
     if (world == 0 || rank >= world) return set_error(BT_ERR_INVALID_ARG, "rank/world out of range");
     int rc = ensure_flat(scene);
     if (rc) return rc;
-    BtLaunch P;
     int output = 0;
     rc = fill_launch(scene, camera_ref, config, render, width, height, 0, P, output);
     if (rc) return rc;
@@ -802,13 +853,57 @@ int bt_debug_primary_mask(bt_scene *scene, uint64_t camera_ref, const bt_config 
     const uint32_t n_tiles = P.tiles_x * P.tiles_y, grid = (n_tiles + world - 1) / world;
     const uint64_t n_blocks = (uint64_t)grid * slices;
     if (n_blocks > 0x7fffffffu) return set_error(BT_ERR_INVALID_ARG, "too many blocks");
-    const std::vector<BtSphereRow> rows = sphere_rows_of(scene->flat.prims);
+    return (int)n_blocks;
+}
+
+int bt_debug_primary_mask(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                          uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint64_t *masks,
+                          uint32_t cap) {
+    BtLaunch P;
+    const int n_blocks = debug_mask_launch(scene, camera_ref, config, render, width, height, slices, rank, world, P);
+    if (n_blocks < 0) return n_blocks;
     if (masks && cap > 0) {
+        const std::vector<BtSphereRow> rows = sphere_rows_of(scene->flat.prims);
         std::vector<uint64_t> all((size_t)n_blocks, ~0ull);
         if (P.any_rects == 0 && P.any_volumes == 0) bt_primary_masks_host(&P, rows.data(), (uint32_t)n_blocks, all.data());
-        std::memcpy(masks, all.data(), sizeof(uint64_t) * (size_t)std::min<uint64_t>(cap, n_blocks));
+        std::memcpy(masks, all.data(), sizeof(uint64_t) * (size_t)std::min<uint64_t>(cap, (uint64_t)n_blocks));
     }
-    return (int)n_blocks;
+    return n_blocks;
+}
+
+int bt_debug_block_masks_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                                uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world,
+                                uint64_t *masks, uint32_t cap) {
+    BtLaunch P;
+    int n_blocks = debug_mask_launch(scene, camera_ref, config, render, width, height, slices, rank, world, P);
+    if (n_blocks < 0) return n_blocks;
+    if (!masks || cap == 0) return n_blocks;
+    if (P.any_rects || P.any_volumes) return set_error(BT_ERR_INVALID_ARG, "the scene does not run the build that reads block masks");
+    int rc = ensure_device(scene);
+    if (rc) return rc;
+    n_blocks = debug_mask_launch(scene, camera_ref, config, render, width, height, slices, rank, world, P);   // (device tables)
+    if (n_blocks < 0) return n_blocks;
+    uint64_t *d = nullptr;
+    BT_HIP(hipMalloc((void **)&d, sizeof(uint64_t) * (size_t)n_blocks));
+    hipError_t e = bt_launch_block_masks(&P, (uint32_t)n_blocks, d, nullptr);
+    if (e == hipSuccess)
+        e = hipMemcpy(masks, d, sizeof(uint64_t) * (size_t)std::min<uint32_t>(cap, (uint32_t)n_blocks), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_error(BT_ERR_DEVICE, hipGetErrorString(e));
+    return n_blocks;
+}
+
+int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                      uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint8_t *out,
+                      uint32_t cap) {
+    BtLaunch P;
+    const int n_blocks = debug_mask_launch(scene, camera_ref, config, render, width, height, slices, rank, world, P);
+    if (n_blocks < 0) return n_blocks;
+    btcull::MaskKey key;
+    P.sphere_rows = nullptr;                              // (a device address: not part of what a host-side test compares)
+    btcull::mask_key(key, P, (uint32_t)n_blocks, scene->rows_generation, nullptr);
+    if (out && cap > 0) std::memcpy(out, &key, std::min<size_t>(cap, sizeof key));
+    return (int)sizeof key;
 }
 
 int bt_render_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
@@ -898,15 +993,19 @@ int bt_preview(const float *rgba_host, uint8_t *rgba8_host, uint32_t width, uint
 
 int bt_scene_trim(bt_scene *scene) {
     if (!scene) return set_error(BT_ERR_INVALID_ARG, "null scene");
-    if (scene->device < 0 || (!scene->d_scratch && !scene->d_host_frame)) return 0;
+    if (scene->device < 0 || (!scene->d_scratch && !scene->d_host_frame && !scene->d_block_masks)) return 0;
     int cur = -1;
     BT_HIP(hipGetDevice(&cur));
     if (cur != scene->device) BT_HIP(hipSetDevice(scene->device));
     BT_HIP(hipDeviceSynchronize());                       // launches that still read the scratch / the cached frame
     if (scene->d_scratch) (void)hipFree(scene->d_scratch);
     if (scene->d_host_frame) (void)hipFree(scene->d_host_frame);
+    if (scene->d_block_masks) (void)hipFree(scene->d_block_masks);
     scene->d_scratch = nullptr;
     scene->d_host_frame = nullptr;
+    scene->d_block_masks = nullptr;
+    scene->block_masks_cap = 0;
+    scene->masks_for = btcull::MaskKey{};
     scene->scratch_bytes = scene->host_frame_bytes = 0;
     scene->scratch_small_streak = 0;
     if (cur != scene->device) BT_HIP(hipSetDevice(cur));

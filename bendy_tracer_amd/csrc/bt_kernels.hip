@@ -27,6 +27,10 @@
 //     loads that broadcast through SGPRs; per-lane lookups (hit primitive, material, light, density) go to tables
 //     staged in LDS; the camera block of the launch parameters is read where it is used, not kept in SGPRs;
 //   * template flags select a build without rect code / without the volume march for scenes that have neither;
+//   * sphere-only launches without volumes: bt_block_mask_kernel (one thread per pixel block, double precision,
+//     bt_cull.hpp) writes which sphere rows each block's camera rays can reach, bt_api.cpp keeps the masks on the scene
+//     handle for as long as their inputs stay the same, and a workgroup of the render kernel whose mask is empty adds the
+//     background's value to its pixels and traces nothing -- one scalar load ahead of everything else;
 //   * no MFMA: there is no dense contraction on this path.
 //
 // Round 3 removed what had lost every measurement of rounds 1 and 2 (the logs stay under profiles/): the lane-owns-pixel
@@ -74,58 +78,7 @@ struct __attribute__((aligned(16))) PathRec { float f[12]; uint32_t w[8]; };
 BT_DEV uint32_t lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
-// ---- where a pixel block lies in the frame ---------------------------------------------------------------------------
-// BtLaunch::slices = NS in {1,2,4,8,16,32}: a 16x16 tile is cut into NS blocks of pxb = 256/NS pixels -- whole 8x8 quadrants
-// down to 64 pixels, then 8x4, 4x4, 4x2 pixels, numbered row-major inside the tile.  Block b of the launch is block
-// b mod NS of the launch's tile b / NS.  The tile (a division by tiles_x: umulhi + one fix-up step) and the block's corner
-// inside it depend on the block alone: computed once per block (wave-uniform: scalar), not once per work item.
-struct BlockGeom { uint32_t NS, LOG_NS, pxb, LOG_PXB, LBW, WMASK; };
-// (block_geom, block_ref and block_extent also run on the host: bt_debug_primary_mask)
-#define BT_HDF static __host__ __device__ __forceinline__
-BT_HDF BlockGeom block_geom(const BtLaunch &P) {
-    BlockGeom g;
-    g.NS = (uint32_t)P.slices;
-    g.LOG_NS = (uint32_t)__builtin_ctz(g.NS);
-    g.pxb = 256u >> g.LOG_NS;                          // pixels per block
-    g.LOG_PXB = 8u - g.LOG_NS;
-    g.LBW = g.pxb >= 32 ? 3u : 2u;                     // log2 of a block row: whole quadrants and 8x4 blocks are 8 pixels wide
-    g.WMASK = (1u << g.LBW) - 1u;
-    return g;
-}
-struct BlockRef { uint32_t px0, py0, tile_ok, slot; };
-BT_HDF BlockRef block_ref(const BtLaunch &P, const BlockGeom &g, uint32_t b) {      // b: block in launch order
-    const uint32_t slot = b >> g.LOG_NS, sub = b & (g.NS - 1u);
-    const uint32_t tile = P.sharded ? (slot * P.world + P.rank) : slot;
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t ty = __umulhi(tile, P.tiles_x_magic), tx = tile - ty * P.tiles_x;      // tile / tiles_x, exact after the fix-up
-#else
-    uint32_t ty = (uint32_t)(((uint64_t)tile * P.tiles_x_magic) >> 32), tx = tile - ty * P.tiles_x;
-#endif
-    if (tx >= P.tiles_x) { ty += 1u; tx -= P.tiles_x; }
-    // corner of block `sub` inside the tile: 128 pixels = the quadrant row `sub`, 64 = quadrant `sub`, below that blocks
-    // of 8x4 / 4x4 / 4x2 pixels numbered row-major
-    uint32_t bx0 = 0, by0 = 0;
-    if (g.pxb == 128) by0 = sub << 3;
-    else if (g.pxb == 64) { bx0 = (sub & 1u) << 3; by0 = (sub >> 1) << 3; }
-    else if (g.pxb < 64) {
-        const uint32_t lbh = g.LOG_PXB - g.LBW, lnbx = 4u - g.LBW;
-        bx0 = (sub & ((1u << lnbx) - 1u)) << g.LBW;
-        by0 = (sub >> lnbx) << lbh;
-    }
-    BlockRef r;
-    r.px0 = tx * BT_TILE_DIM + bx0;
-    r.py0 = ty * BT_TILE_DIM + by0;
-    r.tile_ok = ty < P.tiles_y ? 1u : 0u;
-    r.slot = slot;
-    return r;
-}
-// the block's pixels inside the frame: the rectangle [px0, px0 + nx) x [py0, py0 + ny) (nx = 0 or ny = 0: none).  A block is
-// 16 pixels wide when it holds whole rows of quadrants (pxb >= 128), else 2^LBW; pxb >> log2(width) rows high.
-BT_HDF void block_extent(const BtLaunch &P, const BlockGeom &g, const BlockRef &B, uint32_t &nx, uint32_t &ny) {
-    const uint32_t lw = g.pxb >= 128 ? 4u : g.LBW, bw = 1u << lw, bh = g.pxb >> lw;
-    nx = B.tile_ok && B.px0 < P.width ? (P.width - B.px0 < bw ? P.width - B.px0 : bw) : 0u;
-    ny = B.tile_ok && B.py0 < P.height ? (P.height - B.py0 < bh ? P.height - B.py0 : bh) : 0u;
-}
+// (where a pixel block lies in the frame: block_geom, block_ref, block_extent of bt_cull.hpp, shared with the mask kernel and the host)
 // pixel q of a block: quadrants 1 .. 3 of a 128- or 256-pixel block sit to the right of / below quadrant 0
 struct PixelRef { uint32_t px, py; bool in_frame; };
 BT_DEV PixelRef pixel_of(const BtLaunch &P, const BlockGeom &g, const BlockRef &B, uint32_t q) {
@@ -236,7 +189,49 @@ BT_DEV void sum_blocks(const BtLaunch &P, const BlockGeom &g, uint32_t first, ui
     }
 }
 
+// A block whose mask is empty: every sample of it is one segment that misses, its value is sample_root's with the camera's
+// beta and L.  The workgroup adds that value T times to each pixel's running sum -- the additions sum_block() would perform on
+// the parked values, in the same order -- and traces nothing.
+template <int OUTPUT> BT_DEV void fill_empty_block(const BtLaunch &P) {
+    const BlockGeom G = block_geom(P);
+    const BlockRef B_own = block_ref(P, G, blockIdx.x);
+    const uint32_t T = (uint32_t)P.samples * (uint32_t)(P.subsample_n * P.subsample_n);
+    uint32_t nx = 0, ny = 0;
+    block_extent(P, G, B_own, nx, ny);
+    V3 value;
+    if (OUTPUT == 0) {
+        value = mk(0, 0, 0) + mk(1, 1, 1) * mk(P.root_color);      // L = L + beta * root_color, fresh L and beta
+    } else if (OUTPUT == 1) {
+        value = mk(P.root_albedo);
+    } else {
+        const float fd = P.root_has_albedo ? P.clip_max : __builtin_inff();
+        float depth = (fd - P.clip_min) / (P.clip_max - P.clip_min);
+        depth = fminf(fmaxf(depth, 0.0f), 1.0f);
+        value = mk(depth, depth, depth);
+    }
+    for (uint32_t q = threadIdx.x; q < G.pxb; q += blockDim.x) {
+        const PixelRef r = pixel_of(P, G, B_own, q);
+        if (!r.in_frame) continue;
+        float *o = out_of(P, B_own, r);
+        V3 sum = mk(o[0], o[1], o[2]);
+        for (uint32_t k = 0; k < T; ++k) sum = sum + value;
+        o[0] = sum.x;
+        o[1] = sum.y;
+        o[2] = sum.z;
+    }
+    if (P.counters && threadIdx.x == 0 && nx * ny != 0u) atomicAdd(&P.counters[0], (unsigned long long)(nx * ny) * T);
+}
+
 } // namespace
+
+// One thread per pixel block of a launch: masks[b] = btcull::block_mask (bt_cull.hpp), the rows read through the constant
+// address space.  Microseconds of double-precision work per camera; bt_api.cpp keeps the result on the scene handle.
+__global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t n_blocks, unsigned long long *masks) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_blocks) return;
+    typedef const __attribute__((address_space(4))) BtSphereRow RowK;
+    masks[b] = btcull::block_mask(P, (RowK *)P.sphere_rows, b);
+}
 
 // --------------------------------------------------------------------------------------------
 // The render kernel.  OUTPUT: 0 Full, 1 Albedo, 2 Normal, 3 Depth (tracer/mod.rs:108-115).
@@ -267,6 +262,24 @@ BT_DEV void sum_blocks(const BtLaunch &P, const BlockGeom &g, uint32_t first, ui
 // other builds carry none of their code -- as a run-time switch it cost C3 4 % (profiles/r04u).
 template <int OUTPUT, bool LENS, bool RECTS, bool VOLS, bool PACKED>
 __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WAVES_PER_SIMD_RECTS : (VOLS ? BT_WAVES_PER_SIMD_VOLS : BT_WAVES_PER_SIMD))) void bt_render_kernel(BtLaunch P) {
+    // ---- a block whose camera rays provably reach no sphere (sphere-only builds without volumes; DESIGN.md 5.15) ----
+    // bt_block_mask_kernel has written which sphere rows the block's camera rays can reach: one wave-uniform (scalar) load,
+    // ahead of the LDS staging and its barrier, which an empty block does not need.  The Normal output's miss value depends
+    // on the direction and is not shortcut.
+    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2;
+    if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE)
+        typedef const __attribute__((address_space(4))) unsigned long long MaskK;
+        if (((MaskK *)P.block_masks)[blockIdx.x] == 0ull) {
+            // The empty path reads the launch parameters through a pointer the compiler cannot see through (as the camera
+            // event below does): sharing block_ref() and the like with the code after it kept their inputs in SGPRs across
+            // this branch, and the loop paid with 18 more spill reloads per iteration (profiles/r10).
+            typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
+            BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(C));
+            fill_empty_block<OUTPUT>(*(const BtLaunch *)C);
+            return;
+        }
+    }
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ uint32_t s_waves_done;      // block queue: waves of this workgroup that have parked all their samples
     __shared__ uint32_t s_next_item;       // the workgroup's work queue (next unclaimed (pixel, sample) pair)
@@ -416,55 +429,6 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
     unsigned long long ls_acc[9] = {};
     const unsigned long long ls_all = __ballot(true);
 #endif
-    // ---- a block whose camera rays provably reach no sphere (sphere-only builds without volumes; DESIGN.md 5.15) ----
-    // Every sample of such a block is one segment that misses: its value is sample_root's with the camera's beta and L.
-    // The workgroup adds that value T times to each pixel's running sum -- the additions sum_block() would perform on the
-    // parked values, in the same order -- and traces nothing.  Every wave decides the same (same inputs, same
-    // operations): no barrier.  The Normal output's miss value depends on the direction and is not shortcut.
-    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2;
-    if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE)
-        uint32_t nx = 0, ny = 0;
-        block_extent(P, G, B_own, nx, ny);
-        bool reach = false;                        // may any primary ray of the block hit any sphere row?
-        if (nx != 0u && ny != 0u && P.n_prims > 0) {
-            if (P.n_prims > 64) {
-                reach = true;
-            } else {                               // lanes = sphere rows, one ballot
-                const btcull::Cone K = btcull::primary_cone(P, B_own.px0, B_own.py0, nx, ny);
-                bool mine = false;
-                if ((int)lane < P.n_prims) {
-                    const BtSphereRow R = P.sphere_rows[lane];
-                    mine = btcull::may_hit(K, R.cx, R.cy, R.cz, R.r2);
-                }
-                reach = __ballot(mine) != 0ull;
-            }
-        }
-        if (!reach) {
-            V3 value;
-            if (OUTPUT == 0) {
-                value = mk(0, 0, 0) + mk(1, 1, 1) * mk(P.root_color);      // L = L + beta * root_color, fresh L and beta
-            } else if (OUTPUT == 1) {
-                value = mk(P.root_albedo);
-            } else {
-                const float fd = P.root_has_albedo ? P.clip_max : __builtin_inff();
-                float depth = (fd - P.clip_min) / (P.clip_max - P.clip_min);
-                depth = fminf(fmaxf(depth, 0.0f), 1.0f);
-                value = mk(depth, depth, depth);
-            }
-            for (uint32_t q = threadIdx.x; q < pxb; q += blockDim.x) {
-                const PixelRef r = pixel_of(P, G, B_own, q);
-                if (!r.in_frame) continue;
-                float *o = out_of(P, B_own, r);
-                V3 sum = mk(o[0], o[1], o[2]);
-                for (uint32_t k = 0; k < T; ++k) sum = sum + value;
-                o[0] = sum.x;
-                o[1] = sum.y;
-                o[2] = sum.z;
-            }
-            if (P.counters && threadIdx.x == 0 && nx * ny != 0u) atomicAdd(&P.counters[0], (unsigned long long)(nx * ny) * T);
-            goto block_done;
-        }
-    }
     for (;;) {
         do {                                              // (`continue` below = on to the latch at the end of the iteration)
         if (compacting && dry_lane && pending) continue;  // the queue is empty and this lane has no path: nothing to do
@@ -944,7 +908,6 @@ queue_empty:;
             sum_block(P, G, blockIdx.x, T, park(), lane);
         }
     }
-block_done:;
     if (P.counters) {
         if (LENS) {
             unsigned long long ls = wave_sum(lens_steps);
@@ -1040,32 +1003,35 @@ __global__ __launch_bounds__(256) void bt_preview_kernel(const float4 *rgba, uin
 }
 
 // ---- host-side launchers (called from bt_api.cpp) ---------------------------------------------
-// bt_debug_primary_mask: the masks the sphere-only build computes in its prologue, one per block of the launch `P` describes
-// (blocks in launch order), bit i = sphere row i may be hit; computed here on the host by the same code (bt_cull.hpp).
+// bt_debug_primary_mask: the masks bt_block_mask_kernel writes, one per block of the launch `P` describes (blocks in launch
+// order), bit i = sphere row i may be hit; computed here on the host by the same function (bt_cull.hpp block_mask).
 extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows, uint32_t n_blocks, uint64_t *out) {
-    const BlockGeom G = block_geom(*P);
-    for (uint32_t b = 0; b < n_blocks; ++b) {
-        const BlockRef B = block_ref(*P, G, b);
-        uint32_t nx = 0, ny = 0;
-        block_extent(*P, G, B, nx, ny);
-        uint64_t m = 0;
-        if (nx != 0u && ny != 0u && P->n_prims > 0) {
-            if (P->n_prims > 64) {
-                m = ~0ull;
-            } else {
-                const btcull::Cone K = btcull::primary_cone(*P, B.px0, B.py0, nx, ny);
-                for (int i = 0; i < P->n_prims; ++i)
-                    if (btcull::may_hit(K, rows[i].cx, rows[i].cy, rows[i].cz, rows[i].r2)) m |= 1ull << i;
-            }
-        }
-        out[b] = m;
-    }
+    for (uint32_t b = 0; b < n_blocks; ++b) out[b] = btcull::block_mask(*P, rows, b);
+}
+// Does a launch of `P` run a build that reads BtLaunch::block_masks (the kernel's CULL)?
+extern "C" int bt_launch_reads_masks(const BtLaunch *P, int output) {
+    return !P->any_rects && !P->any_volumes && !P->lens_on && P->wg_blocks <= 1 && output != 2 && P->max_bounces >= 0;
+}
+// 1: bt_api.cpp may keep a launch's masks on the scene handle; 0 (A/B variant -DBT_MASK_NOCACHE): every render computes them
+extern "C" int bt_mask_cache_enabled(void) {
+#ifdef BT_MASK_NOCACHE
+    return 0;
+#else
+    return 1;
+#endif
+}
+extern "C" hipError_t bt_launch_block_masks(const BtLaunch *P, uint32_t n_blocks, uint64_t *masks, hipStream_t stream) {
+    if (n_blocks == 0 || !masks || (P->n_prims > 0 && !P->sphere_rows)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bt_block_mask_kernel, dim3((n_blocks + 255u) / 256u), dim3(256), 0, stream, *P, n_blocks,
+                       (unsigned long long *)masks);
+    return hipGetLastError();
 }
 extern "C" hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned grid, size_t lds_bytes,
                                        hipStream_t stream) {
     // grid = tiles to render; a tile is P->slices workgroups (see the mapping in the kernel)
     const bool packed = P->wg_blocks > 1;          // bt_api.cpp packs launches without the lens only
     if (packed && P->lens_on) return hipErrorInvalidValue;
+    if (bt_launch_reads_masks(P, output) && !P->block_masks) return hipErrorInvalidValue;   // no masks, no launch
     dim3 g(packed ? P->n_workgroups : grid * (unsigned)P->slices), b(256);
     // scene classes: bit 0 = some sphere carries a volume (volume.json, cloud.json), bit 1 = rects / cuboids present
     // (the Cornell boxes); scene.json is class 0

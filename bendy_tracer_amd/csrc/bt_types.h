@@ -237,4 +237,7 @@ struct BtLaunch {
                                       // rounds (bt_kernels.hip), 0 = none: lanes leave the loop when the queue is empty
     uint32_t log_rows, row_mask;      // packed: a block's T = samples * n^2 samples are padded to 2^log_rows rows in the queue and in
                                       // scratch, row_mask = 2^log_rows - 1; not packed: row_mask = 0xffffffff
+    // Sphere-only launches without volumes, lens and packing (bt_kernels.hip CULL): per block of the launch, in launch order,
+    // the sphere rows its camera rays can reach (bt_cull.hpp block_mask, written by bt_block_mask_kernel); else null
+    const uint64_t *block_masks;
 };

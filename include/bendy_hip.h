@@ -158,13 +158,29 @@ int bt_scene_data_count(const bt_scene *scene);
  * writes up to `cap` floats, returns the number available. */
 int bt_scene_export_prims(const bt_scene *scene, float *out, int cap);
 /* For tests: the per-block sphere masks of the sphere-only build without volumes, computed on the host
- * by the kernel's own code.  Blocks of a launch with `slices` (1, 2, 4, ..., 32) blocks per 16x16 tile, in launch order:
+ * by the mask kernel's own code.  Blocks of a launch with `slices` (1, 2, 4, ..., 32) blocks per 16x16 tile, in launch order:
  * tile-major over the frame, or over rank `rank`'s tiles when world > 1.  Bit i set = sphere row i may be hit by a primary
  * ray of the block; a block with no bit set traces nothing.  Writes up to `cap` masks (masks may be NULL) and returns the
  * number of blocks; every bit is set for scenes that do not run that build. */
 int bt_debug_primary_mask(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
                           uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint64_t *masks,
                           uint32_t cap);
+
+/* For tests of what a handle keeps between renders: moves an object (translation = 3 floats of transform_world, or NULL)
+ * and / or resizes a sphere (radius > 0) IN PLACE; the next render flattens and uploads the tables again.  The JSON that
+ * bt_scene_save / bt_scene_to_json write is not updated. */
+int bt_debug_set_object(bt_scene *scene, uint64_t object_ref, const float *translation, float radius);
+/* For tests: the same masks as bt_block_mask_kernel writes them on the current device (the kernel the render launches read
+ * their masks from), copied back.  Same arguments and return value as bt_debug_primary_mask; BT_ERR_INVALID_ARG for a scene
+ * that does not run that build. */
+int bt_debug_block_masks_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                                uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world,
+                                uint64_t *masks, uint32_t cap);
+/* For tests: the bytes of the key under which a handle keeps such a launch's masks between renders (stream = NULL, no
+ * device address): any input the masks depend on must change them.  Writes up to `cap` bytes, returns the key's size. */
+int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                      uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint8_t *out,
+                      uint32_t cap);
 
 /* --- Tracer::render (tracer/mod.rs:179-202) ----------------------------------------
  * Adds `samples * n^2` radiance samples per pixel into the RGB channels of `rgba`
