@@ -17,14 +17,30 @@ def _rot(rng, spread):
     return ry @ rx @ rz
 
 
-def sphere_scene(seed, n_spheres=None, focus=None):
+ROOT_KEYS = {"Emissive": 1, "Flat": 7, "Diffuse": 8, "Metallic": 9, "Glass": 10}
+
+
+def sphere_scene(seed, n_spheres=None, focus=None, cam_post=None, focal_length=None, fstop=None, focus_dist=None,
+                 root=None):
     """A camera with a random orientation and spheres placed so that many pixel blocks see nothing and many see a
-    sphere's silhouette: in front, off to the sides, behind the camera, and now and then around the camera."""
+    sphere's silhouette: in front, off to the sides, behind the camera, and now and then around the camera.
+
+    The optional arguments reach the inputs the ordinary camera never has (tests/test_cull_edges.py); left at None they
+    change nothing, and none of them changes the number or order of the random draws, so the spheres of a seed stay
+    where they are:
+    cam_post: 3x3, multiplied onto the random rotation (scale, mirror, shear); the spheres are placed along the
+    rotation's own axes.  focal_length, fstop, focus_dist: replace the drawn values (focus_dist only with focus).
+    root: the root material's kind, "Flat" / "Diffuse" / "Metallic" / "Glass" / "Emissive" (rows 7 - 10 are added for
+    the first four, with colours from a generator of their own)."""
     rng = np.random.default_rng(seed)
     n = int(rng.integers(1, 9)) if n_spheres is None else n_spheres
     if focus is None:
         focus = bool(rng.uniform() < 0.5)
-    cam_m = _rot(rng, 0.6).astype(np.float32)
+    rot = _rot(rng, 0.6)
+    cam_m = rot.astype(np.float32)
+    if cam_post is not None:
+        cam_m = (rot @ np.asarray(cam_post, np.float64).reshape(3, 3)).astype(np.float32)
+        rot = rot.astype(np.float32)
     cam_t = rng.uniform(-3, 3, 3).astype(np.float32)
     col = lambda: dict(zip("rgb", [float(v) for v in rng.uniform(0.1, 0.9, 3)]))
     data = {"0": {"inner": {"Material": {"Flat": {"albedo": {"r": 0.0, "g": 0.0, "b": 0.0}}}}},
@@ -43,10 +59,27 @@ def sphere_scene(seed, n_spheres=None, focus=None):
                            "transform": {"transform_world": a, "transform_local": a, "transform_parent": None},
                            "inner": inner, "children": None}
 
-    add({"Camera": {"sensor_size": 0.024, "focal_length": float(rng.uniform(0.02, 0.06)), "aspect_ratio": 1.5,
-                    "fstop": float(rng.uniform(0.5, 4.0)), "focus": float(rng.uniform(3, 12)) if focus else None}},
-        cam_m, cam_t, tag="camera")
-    fwd, right, up = -cam_m[:, 2], cam_m[:, 0], cam_m[:, 1]
+    root_material = 1
+    if root is not None:
+        rng_root = np.random.default_rng([seed, 0x7007])
+        rcol = lambda: dict(zip("rgb", [float(v) for v in rng_root.uniform(0.1, 0.9, 3)]))
+        data["7"] = {"inner": {"Material": {"Flat": {"albedo": rcol()}}}}
+        data["8"] = {"inner": {"Material": {"Diffuse": {"albedo": rcol(), "roughness": 0.5}}}}
+        data["9"] = {"inner": {"Material": {"Metallic": {"albedo": rcol(), "roughness": 0.2}}}}
+        data["10"] = {"inner": {"Material": {"Glass": {"albedo": rcol(), "roughness": 0.02, "ior": 1.4}}}}
+        root_material = ROOT_KEYS[root]
+
+    cam = {"sensor_size": 0.024, "focal_length": float(rng.uniform(0.02, 0.06)), "aspect_ratio": 1.5,
+           "fstop": float(rng.uniform(0.5, 4.0)), "focus": float(rng.uniform(3, 12)) if focus else None}
+    if focal_length is not None:
+        cam["focal_length"] = float(focal_length)
+    if fstop is not None:
+        cam["fstop"] = float(fstop)
+    if focus_dist is not None and focus:
+        cam["focus"] = float(focus_dist)
+    add({"Camera": cam}, cam_m, cam_t, tag="camera")
+    axes = cam_m if cam_post is None else rot
+    fwd, right, up = -axes[:, 2], axes[:, 0], axes[:, 1]
     for i in range(n):
         kind = rng.uniform()
         r = float(rng.uniform(0.2, 1.5))
@@ -63,7 +96,7 @@ def sphere_scene(seed, n_spheres=None, focus=None):
             c = cam_t - up * (r + rng.uniform(0.5, 3)) + fwd * rng.uniform(0, 10)
         mat = 6 if i == 0 else int(rng.integers(2, 6))
         add({"Sphere": {"material": mat, "volume": None, "radius": r}}, np.eye(3), c, flags=1 if i == 0 else 0)
-    return json.dumps({"roots": [], "root_material": 1, "objects": {"collection": objects, "next_key": len(objects)},
+    return json.dumps({"roots": [], "root_material": root_material, "objects": {"collection": objects, "next_key": len(objects)},
                        "data": {"collection": data, "next_key": len(data)}})
 
 
@@ -91,7 +124,12 @@ def spheres_of(doc):
 
 def primary_rays(cam, w, h, px, py, n, jit, disk):
     """Camera rays (bt_kernels.hip camera event) in float32 for pixels (px, py), sub-pixel cells of Subsample(n),
-    jitter fractions jit (k x 2, in [0, 1)) and aperture points disk (m x 2: angle, radius fraction)."""
+    jitter fractions jit (k x 2, in [0, 1)) and aperture points disk (m x 2: angle, radius fraction).
+
+    `cam["m"]` may be any matrix, as in the kernel: the direction M d_cam is normalised BEFORE the focus distance
+    multiplies it, the lens offset M (defocus * aperture) is not (under a matrix of scale s the lens is s times as
+    wide, the focus plane stays where it is).  Nothing here assumes |yrot| <= pi/2: beyond it d_cam.z changes sign, the
+    ray points behind the camera and focus / |d_cam.z| passes its pole, as in the kernel."""
     pw, ph = f32(2.0) * (f32(1.0) / f32(w)), f32(2.0) * (f32(1.0) / f32(h))
     sub = f32(1.0) / f32(n) if n > 1 else f32(1.0)
     umin, vmin = f32(-0.5) * pw * sub, f32(-0.5) * ph * sub
