@@ -150,6 +150,7 @@ EXPORTS = [
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
     "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_set_object",
+    "bt_render_guided_device",
 ]
 
 
@@ -197,6 +198,8 @@ def _load():
                             C.c_uint32, C.c_uint64]
     L.bt_render_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp, C.c_uint32,
                                    C.c_uint32, C.c_uint64, vp]
+    L.bt_render_guided_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp, vp, vp, vp,
+                                          C.c_uint32, C.c_uint32, C.c_uint64, vp]
     L.bt_shard_floats.restype = C.c_size_t
     L.bt_shard_floats.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.bt_render_shard_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp,
@@ -485,6 +488,38 @@ class Tracer:
         _check(rc)
         if rc == Status.InProgress:
             buffer.inc_samples(config.samples * nn)  # mod.rs:199
+        return Status(rc)
+
+    def render_guided(self, scene: Scene, camera: int, config: RenderConfig, color: Buffer, albedo: Optional[Buffer] = None,
+                      normal: Optional[Buffer] = None, depth: Optional[Buffer] = None, seed: Optional[int] = None,
+                      sample_base: Optional[int] = None) -> Status:
+        """EXTENSION, not in the reference (bt_render_guided_device): one pass that adds the colour samples
+        to `color` and, from the same paths, the Output.Albedo / Normal / Depth values to the guide buffers that are given
+        -- every buffer ends up bit-identical to what `render` writes into it with the corresponding output.  GPU buffers
+        of one size only; the effective output must be Output.Full; `seed` and `sample_base` default as in `render`
+        (taken from `color`)."""
+        seed = self.DEFAULT_SEED if seed is None else seed
+        output = config.output if config.output is not None else self.config.output
+        if int(output) != int(Output.Full):
+            raise BendyError(-1, f"render_guided renders Output.Full plus its guides, not output {int(output)}")
+        guides = [albedo, normal, depth]
+        for b in [color] + [g for g in guides if g is not None]:
+            if b.device == "cpu":
+                raise BendyError(-1, "render_guided needs device-resident buffers (there is no host-buffer variant)")
+            if (b.width, b.height) != (color.width, color.height):
+                raise BendyError(-1, f"buffer of {b.width}x{b.height} next to a {color.width}x{color.height} colour buffer")
+        nn = config.subsample.subpixel_count()
+        if sample_base is None:
+            sample_base = (color.samples + nn - 1) // nn
+        c, r = _c_configs(self.config, config, sample_base)
+        import torch
+        rc = lib.bt_render_guided_device(scene._h, camera, C.byref(c), C.byref(r), color.data.data_ptr(),
+                                         *[g.data.data_ptr() if g is not None else None for g in guides], color.width,
+                                         color.height, seed, torch.cuda.current_stream().cuda_stream)
+        _check(rc)
+        if rc == Status.InProgress:
+            for b in [color] + [g for g in guides if g is not None]:
+                b.inc_samples(config.samples * nn)
         return Status(rc)
 
     def primary_masks(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1):

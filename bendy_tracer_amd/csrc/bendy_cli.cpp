@@ -11,7 +11,8 @@
 // --lens x,y,z,rs,step,radius[,max_steps] for the gravitational-lens EXTENSION (not in the reference; bt_lens), and
 // --denoise [--denoise-guide-samples N] for the denoiser EXTENSION (not in the reference; bt_denoiser): after the loop the
 // albedo, normal and depth AOVs are rendered with N x subsample^2 rays per pixel (same seed) and the screenshot is the
-// denoised mean.
+// denoised mean.  --denoise-inline (extension too; bt_render_guided_device): every call of the progressive loop renders the colour
+// AND the three guides in one pass into four device frames, and the screenshot is the denoised mean of those.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -83,6 +84,7 @@ struct Args {
     bt_lens lens{};
     bool denoise = false;
     unsigned denoise_guide_samples = 4;
+    bool denoise_inline = false;
 };
 
 void usage() {
@@ -92,7 +94,9 @@ void usage() {
                  "       [--seed N] [--save-scene PATH] [--device N] [--quiet]\n"
                  "       [--samples-per-call 1] [--no-screenshot] [--stats-json PATH] [--shard rank,world]   (measurement harness)\n"
                  "       [--lens x,y,z,rs,step,radius[,max_steps]]   (extension: not in the reference)\n"
-                 "       [--denoise] [--denoise-guide-samples 4]   (extension: not in the reference; --output full only)\n");
+                 "       [--denoise] [--denoise-guide-samples 4]   (extension: not in the reference; --output full only)\n"
+                 "       [--denoise-inline]   (extension: colour and guides in one pass per call; --output full only, not with\n"
+                 "                             --denoise, --shard or --lens)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -138,6 +142,7 @@ Args parse(int argc, char **argv) {
             a.has_lens = true;
         }
         else if (k == "--denoise") a.denoise = true;
+        else if (k == "--denoise-inline") a.denoise_inline = true;
         else if (k == "--denoise-guide-samples") a.denoise_guide_samples = (unsigned)std::strtoul(val().c_str(), nullptr, 10);
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
@@ -147,6 +152,10 @@ Args parse(int argc, char **argv) {
     if (a.denoise && a.output != "full") die("--denoise needs --output full");
     if (a.denoise && a.shard_world > 1) die("--denoise does not apply to a --shard run");
     if (a.denoise && a.denoise_guide_samples == 0) die("--denoise-guide-samples must be positive");
+    if (a.denoise_inline && a.output != "full") die("--denoise-inline needs --output full");
+    if (a.denoise_inline && a.denoise) die("--denoise-inline and --denoise exclude each other");
+    if (a.denoise_inline && a.shard_world > 1) die("--denoise-inline does not apply to a --shard run");
+    if (a.denoise_inline && a.has_lens) die("--denoise-inline has no builds for --lens");
     return a;
 }
 
@@ -211,6 +220,14 @@ int main(int argc, char **argv) {
     hip_check(hipMalloc((void **)&d_rgba8, n_px * 4), "hipMalloc");
     hip_check(hipMemcpy(d_frame, init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
 
+    // --denoise-inline (extension): the guides' frames and the denoised mean; every call below fills all four in one pass
+    float *d_guides[4] = {nullptr, nullptr, nullptr, nullptr};          // albedo, normal, depth, denoised mean
+    if (args.denoise_inline)
+        for (int g = 0; g < 4; ++g) {
+            hip_check(hipMalloc((void **)&d_guides[g], n_px * 16), "hipMalloc");
+            hip_check(hipMemcpy(d_guides[g], init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
+        }
+
     // main.rs:245-254: one sample per call while buffer.samples() < max_samples
     unsigned buffer_samples = 0;
     double sum_delta = 0.0;
@@ -220,7 +237,10 @@ int main(int argc, char **argv) {
         rc.samples = std::min(args.samples_per_call, std::max(1u, (args.samples - buffer_samples) / nn));
         rc.sample_base = (buffer_samples + nn - 1) / nn;
         const auto t0 = std::chrono::steady_clock::now();
-        int st = sharded ? bt_render_shard_device(scene, camera, &cfg, &rc, d_frame, args.width, args.height, args.shard_rank,
+        int st = args.denoise_inline
+                     ? bt_render_guided_device(scene, camera, &cfg, &rc, d_frame, d_guides[0], d_guides[1], d_guides[2], args.width,
+                                               args.height, args.seed, nullptr)
+                 : sharded ? bt_render_shard_device(scene, camera, &cfg, &rc, d_frame, args.width, args.height, args.shard_rank,
                                                   args.shard_world, args.seed, nullptr)
                          : bt_render_device(scene, camera, &cfg, &rc, d_frame, args.width, args.height, args.seed, nullptr);
         check(st, "bt_render_device");
@@ -277,7 +297,17 @@ int main(int argc, char **argv) {
     // --denoise (extension): the guides of the same frame into fresh buffers, then the screenshot shows the denoised mean
     float *d_shown = d_frame;
     unsigned shown_samples = buffer_samples ? buffer_samples : 1;
-    float *d_guides[4] = {nullptr, nullptr, nullptr, nullptr};          // albedo, normal, depth, denoised mean
+    if (args.denoise_inline && !args.no_screenshot) {
+        bt_denoiser *dn = bt_denoiser_new();
+        check(bt_denoise_device(dn, d_frame, shown_samples, d_guides[0], shown_samples, d_guides[1], shown_samples, d_guides[2],
+                                shown_samples, d_guides[3], args.width, args.height, nullptr, nullptr),
+              "bt_denoise_device");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bt_denoiser_free(dn);
+        d_shown = d_guides[3];
+        shown_samples = 1;                                  // the denoised buffer holds a mean
+        std::fprintf(stderr, "denoised with in-pass guides of %u samples\n", buffer_samples);
+    }
     if (args.denoise && !args.no_screenshot) {
         for (int g = 0; g < 4; ++g) {
             hip_check(hipMalloc((void **)&d_guides[g], n_px * 16), "hipMalloc");

@@ -391,9 +391,11 @@ int fill_launch(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const bt
     return 0;
 }
 
+// `guides` (bt_render_guided_device, an extension): null, or the albedo / normal / depth frames of a guided render, any of them
+// null; the caller has checked that the effective output is BT_OUTPUT_FULL and that no lens is set.
 int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const bt_render_config *rc, float *out_device,
                   uint32_t width, uint32_t height, uint32_t rank, uint32_t world, bool sharded, uint64_t seed,
-                  hipStream_t stream) {
+                  hipStream_t stream, float *const *guides = nullptr) {
     if (!s || !cfg || !rc || !out_device) return set_error(BT_ERR_INVALID_ARG, "null argument");
     if (rc->samples == 0) return BT_DONE;                              // mod.rs:186-188
     if (world == 0 || rank >= world) return set_error(BT_ERR_INVALID_ARG, "rank/world out of range");
@@ -407,6 +409,17 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
     P.world = world;
     P.sharded = sharded ? 1 : 0;
     P.out = out_device;
+    // Guided render: the OUTPUT == 4 builds park 12 more bytes per sample for the albedo, 12 for the normal and 4 for the depth,
+    // each only if its frame is given.  Without any guide it is the Full render, build and all.
+    const bool guided = guides && (guides[0] || guides[1] || guides[2]);
+    uint64_t sample_bytes = 3 * sizeof(float);                            // bytes parked per sample: 12 for the colour value
+    if (guided) {
+        output = 4;
+        for (int g = 0; g < 3; ++g) {
+            P.guide_out[g] = guides[g];
+            if (guides[g]) sample_bytes += (g == 2 ? 1 : 3) * sizeof(float);
+        }
+    }
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
     const uint32_t grid = sharded ? (n_tiles + world - 1) / world : n_tiles;
 
@@ -467,7 +480,7 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
         return true;
     };
     const uint64_t T_all = (uint64_t)P.samples * nn;
-    const uint64_t per_sample = px_launch * nn * 3 * sizeof(float);          // 12 B per parked sample value
+    const uint64_t per_sample = px_launch * nn * sample_bytes;               // 12 B per parked sample value (+ the guides')
     const uint64_t cap = tune.scratch_cap_bytes ? tune.scratch_cap_bytes : kDefaultScratchCap;
     if (per_sample * chunk > cap) chunk = (uint32_t)std::max<uint64_t>(1, cap / per_sample);
     // the parked values need device memory; when it cannot be had, render fewer samples per launch (there is no path that
@@ -545,7 +558,7 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
         uint32_t log_rows = 0;                                   // T padded to a power of two: rows of a block in the queue
         while ((1ull << log_rows) < T_launch) log_rows += 1;
         const uint64_t wg_items = (per_wg * (256u / S)) << log_rows;
-        const uint64_t need = (uint64_t)wg_slots * wg_items * 3 * sizeof(float);
+        const uint64_t need = (uint64_t)wg_slots * wg_items * sample_bytes;
         if (blocks > wg_slots && blocks <= 0x7fffffffu && wg_items <= items_max &&
             (need <= s->scratch_bytes || ensure_scratch(need))) {
             P.slices = (int32_t)S;
@@ -564,7 +577,19 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
         }
         P.scratch = s->d_scratch;
     }
-    const uint64_t parked_bytes = px_launch * T_all * 3 * sizeof(float);
+    const uint64_t parked_bytes = px_launch * T_all * sample_bytes;
+    if (guided) {
+        // the guides' planes behind the colour values of the launch, each indexed like them (bt_types.h guide_scratch)
+        const uint64_t values = P.wg_blocks > 1 ? (uint64_t)P.n_workgroups * (((uint64_t)P.wg_blocks * (256u / (uint32_t)P.slices)) << P.log_rows)
+                                                : px_launch * (uint64_t)chunk * nn;
+        float *plane = P.scratch + values * 3;
+        for (int g = 0; g < 3; ++g) {
+            P.guide_scratch[g] = guides[g] ? plane : nullptr;
+            if (guides[g]) plane += values * (g == 2 ? 1 : 3);
+        }
+        if ((uint64_t)((char *)plane - (char *)P.scratch) > s->scratch_bytes)
+            return set_error(BT_ERR_DEVICE, "the guides' parked values do not fit the scratch");
+    }
 
     if (lds_bytes > 158 * 1024)
         return set_error(BT_ERR_INVALID_ARG, "scene tables (" + std::to_string(s->flat.lds_bytes()) +
@@ -910,6 +935,24 @@ int bt_render_device(bt_scene *scene, uint64_t camera_ref, const bt_config *conf
                      float *rgba_device, uint32_t width, uint32_t height, uint64_t seed, void *stream) {
     return render_common(scene, camera_ref, config, render, rgba_device, width, height, 0, 1, false, seed,
                          (hipStream_t)stream);
+}
+
+int bt_render_guided_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                            float *color_device, float *albedo_device, float *normal_device, float *depth_device,
+                            uint32_t width, uint32_t height, uint64_t seed, void *stream) {
+    // everything that can be refused is refused before the device is touched
+    if (!scene || !config || !render || !color_device) return set_error(BT_ERR_INVALID_ARG, "null argument");
+    const int output = render->has_output ? render->output : config->output;
+    if (output != BT_OUTPUT_FULL)
+        return set_error(BT_ERR_INVALID_ARG, "a guided render is the Full output plus its guides: the effective output must be BT_OUTPUT_FULL");
+    float *const frames[4] = {color_device, albedo_device, normal_device, depth_device};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (frames[i] && frames[i] == frames[j]) return set_error(BT_ERR_INVALID_ARG, "two frames of a guided render are the same buffer");
+    if (scene->lens_on) return set_error(BT_ERR_UNSUPPORTED, "the lens extension has no guided builds");
+    if (render->samples == 0) return BT_DONE;                          // mod.rs:186-188
+    return render_common(scene, camera_ref, config, render, color_device, width, height, 0, 1, false, seed, (hipStream_t)stream,
+                         frames + 1);
 }
 
 int bt_render(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,

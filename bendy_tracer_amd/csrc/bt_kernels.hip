@@ -67,6 +67,12 @@ namespace {
 
 // A parked sample value: 12 bytes (round 1 parked a float4 with an unused w -- a quarter of the block queue's HBM traffic).
 struct Parked { float x, y, z; };
+// Guided render (EXTENSION, OUTPUT == 4): a parked depth value -- one float, added to all three channels (buffer.rs:172-178)
+struct Parked1 { float x; };
+BT_DEV V3 v3_of(const Parked &v) { return mk(v.x, v.y, v.z); }
+BT_DEV V3 v3_of(const Parked1 &v) { return mk(v.x, v.x, v.x); }
+BT_DEV V3 shfl_v3(const Parked &v, int from) { return mk(__shfl(v.x, from, 64), __shfl(v.y, from, 64), __shfl(v.z, from, 64)); }
+BT_DEV V3 shfl_v3(const Parked1 &v, int from) { const float d = __shfl(v.x, from, 64); return mk(d, d, d); }
 
 enum { EV_GEN = 0, EV_DIFFUSE = 1, EV_METALLIC = 2, EV_GLASS = 3, EV_VOLUME = 4 };
 
@@ -89,35 +95,38 @@ BT_DEV PixelRef pixel_of(const BtLaunch &P, const BlockGeom &g, const BlockRef &
     return r;
 }
 // the pixel's running sum: row-major frame, or this rank's tile-major shard
-BT_DEV float *out_of(const BtLaunch &P, const BlockRef &B, const PixelRef &r) {
-    return P.sharded ? P.out + ((size_t)B.slot * (BT_TILE_DIM * BT_TILE_DIM) + (r.py & 15u) * BT_TILE_DIM + (r.px & 15u)) * 4
-                     : P.out + ((size_t)r.py * P.width + r.px) * 4;
+// (`frame` = BtLaunch::out, or one of the guide frames of a guided render)
+BT_DEV float *out_of(const BtLaunch &P, float *frame, const BlockRef &B, const PixelRef &r) {
+    return P.sharded ? frame + ((size_t)B.slot * (BT_TILE_DIM * BT_TILE_DIM) + (r.py & 15u) * BT_TILE_DIM + (r.px & 15u)) * 4
+                     : frame + ((size_t)r.py * P.width + r.px) * 4;
 }
 
 // `*r += pixel.r` (buffer.rs:159-164) for every parked sample of block b's pixels, in sample order -- the additions a
 // lane that owned the pixel would perform in a register, in the same order, hence the same bits.  Executed by ONE wave
 // (`lane` = 0 .. 63); src = the block's parked values, src[k * pxb + pixel].
-BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_t T, const Parked *src, uint32_t lane) {
+// PK = Parked, or Parked1 for the depth plane of a guided render; `frame` = the frame the plane is added to.
+template <class PK>
+BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_t T, const PK *src, uint32_t lane, float *frame) {
     const BlockRef B = block_ref(P, g, b);
     const uint32_t pxb = g.pxb;
     if (pxb >= 64) {
         for (uint32_t q = lane; q < pxb; q += 64) {
             const PixelRef r = pixel_of(P, g, B, q);
             if (!r.in_frame) continue;
-            float *o = out_of(P, B, r);
-            const Parked *s = src + q;
+            float *o = out_of(P, frame, B, r);
+            const PK *s = src + q;
             V3 sum = mk(o[0], o[1], o[2]);
             uint32_t kk = 0;
             for (; kk + BT_SUM_BATCH <= T; kk += BT_SUM_BATCH) {   // BT_SUM_BATCH loads in flight, additions strictly in order
-                Parked v[BT_SUM_BATCH];
+                PK v[BT_SUM_BATCH];
 #pragma unroll
                 for (int j = 0; j < BT_SUM_BATCH; ++j) v[j] = s[(size_t)(kk + j) * pxb];
 #pragma unroll
-                for (int j = 0; j < BT_SUM_BATCH; ++j) sum = sum + mk(v[j].x, v[j].y, v[j].z);
+                for (int j = 0; j < BT_SUM_BATCH; ++j) sum = sum + v3_of(v[j]);
             }
             for (; kk < T; ++kk) {
-                const Parked v = s[(size_t)kk * pxb];
-                sum = sum + mk(v.x, v.y, v.z);
+                const PK v = s[(size_t)kk * pxb];
+                sum = sum + v3_of(v);
             }
             o[0] = sum.x;
             o[1] = sum.y;
@@ -129,22 +138,22 @@ BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_
         const uint32_t J = 64u >> g.LOG_PXB, q = lane & (pxb - 1u), jl = lane >> g.LOG_PXB;
         const PixelRef r = pixel_of(P, g, B, q);
         const bool owner = jl == 0 && r.in_frame;
-        float *o = out_of(P, B, r);
-        const Parked *s = src + q;
+        float *o = out_of(P, frame, B, r);
+        const PK *s = src + q;
         V3 sum = mk(0.0f, 0.0f, 0.0f);
         if (owner) sum = mk(o[0], o[1], o[2]);
         for (uint32_t kk = 0; kk < T; kk += 8 * J) {
-            Parked v[8];
+            PK v[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const uint32_t k2 = kk + (uint32_t)u * J + jl;
-                v[u] = k2 < T ? s[(size_t)k2 * pxb] : Parked{0.0f, 0.0f, 0.0f};
+                v[u] = k2 < T ? s[(size_t)k2 * pxb] : PK{};
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
                 for (uint32_t jj = 0; jj < J; ++jj) {
                     const int from = (int)(q + jj * pxb);
-                    const V3 val = mk(__shfl(v[u].x, from, 64), __shfl(v[u].y, from, 64), __shfl(v[u].z, from, 64));
+                    const V3 val = shfl_v3(v[u], from);
                     if (kk + (uint32_t)u * J + jj < T) sum = sum + val;
                 }
         }
@@ -160,28 +169,29 @@ BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_
 // A workgroup of a packed launch (BtLaunch::wg_blocks > 1) owns the blocks first, first + stride, ...: `n` of them, parked
 // back to back.  All its threads sum, one pixel each at a time, BT_SUM_BATCH parked values in flight, additions strictly in
 // sample order.
+template <class PK>
 BT_DEV void sum_blocks(const BtLaunch &P, const BlockGeom &g, uint32_t first, uint32_t stride, uint32_t n, uint32_t T,
-                       const Parked *src, uint32_t thread, uint32_t n_threads) {
+                       const PK *src, uint32_t thread, uint32_t n_threads, float *frame) {
     const uint32_t LOG_ROWS = P.log_rows;              // a block's samples are padded to 2^log_rows rows of pxb parked values
     for (uint32_t p = thread; p < (n << g.LOG_PXB); p += n_threads) {
         const uint32_t j = p >> g.LOG_PXB, q = p & (g.pxb - 1u);
         const BlockRef B = block_ref(P, g, first + j * stride);
         const PixelRef r = pixel_of(P, g, B, q);
         if (!r.in_frame) continue;
-        float *o = out_of(P, B, r);
-        const Parked *s = src + ((size_t)j << (LOG_ROWS + g.LOG_PXB)) + q;
+        float *o = out_of(P, frame, B, r);
+        const PK *s = src + ((size_t)j << (LOG_ROWS + g.LOG_PXB)) + q;
         V3 sum = mk(o[0], o[1], o[2]);
         uint32_t kk = 0;
         for (; kk + BT_SUM_BATCH <= T; kk += BT_SUM_BATCH) {
-            Parked v[BT_SUM_BATCH];
+            PK v[BT_SUM_BATCH];
 #pragma unroll
             for (int u = 0; u < BT_SUM_BATCH; ++u) v[u] = s[(size_t)(kk + u) << g.LOG_PXB];
 #pragma unroll
-            for (int u = 0; u < BT_SUM_BATCH; ++u) sum = sum + mk(v[u].x, v[u].y, v[u].z);
+            for (int u = 0; u < BT_SUM_BATCH; ++u) sum = sum + v3_of(v[u]);
         }
         for (; kk < T; ++kk) {
-            const Parked v = s[(size_t)kk << g.LOG_PXB];
-            sum = sum + mk(v.x, v.y, v.z);
+            const PK v = s[(size_t)kk << g.LOG_PXB];
+            sum = sum + v3_of(v);
         }
         o[0] = sum.x;
         o[1] = sum.y;
@@ -212,7 +222,7 @@ template <int OUTPUT> BT_DEV void fill_empty_block(const BtLaunch &P) {
     for (uint32_t q = threadIdx.x; q < G.pxb; q += blockDim.x) {
         const PixelRef r = pixel_of(P, G, B_own, q);
         if (!r.in_frame) continue;
-        float *o = out_of(P, B_own, r);
+        float *o = out_of(P, P.out, B_own, r);
         V3 sum = mk(o[0], o[1], o[2]);
         for (uint32_t k = 0; k < T; ++k) sum = sum + value;
         o[0] = sum.x;
@@ -234,7 +244,8 @@ __global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t
 }
 
 // --------------------------------------------------------------------------------------------
-// The render kernel.  OUTPUT: 0 Full, 1 Albedo, 2 Normal, 3 Depth (tracer/mod.rs:108-115).
+// The render kernel.  OUTPUT: 0 Full, 1 Albedo, 2 Normal, 3 Depth (tracer/mod.rs:108-115); 4 = Full plus the three others
+// from the same paths, each into a frame of its own (guided render, an EXTENSION: bt_render_guided_device).
 // Block = 256 threads; 7 waves per SIMD caps the allocation at 72 VGPRs (round 2, without the SLP vectorizer;
 // profiles/r03c/ab_waves_noslp.log, ab_waves_per_class.log).
 #ifndef BT_WAVES_PER_SIMD
@@ -249,6 +260,9 @@ __global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t
 #ifndef BT_WAVES_PER_SIMD_LENS
 #define BT_WAVES_PER_SIMD_LENS 6       // lens builds: 80 VGPRs + ~100 B of scratch per lane still beat 4 waves without
 #endif                                 // scratch (665 -> 719 Msamples/s, profiles/r01g/ab_lens_waves.log)
+#ifndef BT_WAVES_PER_SIMD_GUIDED_RECTS
+#define BT_WAVES_PER_SIMD_GUIDED_RECTS 7   // guided (OUTPUT == 4) rect builds without volumes: own knob for A/B runs
+#endif
 // LENS switches the (non-reference, default-off) gravitational-lens extension of bt_device.hpp in.
 #ifndef BT_SKIP_DIR
 #define BT_SKIP_DIR 1          // a wave of pass-through march steps skips the direction sampling
@@ -261,12 +275,13 @@ __global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t
 // PACKED = true: the builds for packed launches (BtLaunch::wg_blocks > 1; not with the lens extension), so that the
 // other builds carry none of their code -- as a run-time switch it cost C3 4 % (profiles/r04u).
 template <int OUTPUT, bool LENS, bool RECTS, bool VOLS, bool PACKED>
-__global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WAVES_PER_SIMD_RECTS : (VOLS ? BT_WAVES_PER_SIMD_VOLS : BT_WAVES_PER_SIMD))) void bt_render_kernel(BtLaunch P) {
+__global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER_SIMD_GUIDED_RECTS : LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WAVES_PER_SIMD_RECTS : (VOLS ? BT_WAVES_PER_SIMD_VOLS : BT_WAVES_PER_SIMD))) void bt_render_kernel(BtLaunch P) {
     // ---- a block whose camera rays provably reach no sphere (sphere-only builds without volumes) ----
     // bt_block_mask_kernel has written which sphere rows the block's camera rays can reach: one wave-uniform (scalar) load,
     // ahead of the LDS staging and its barrier, which an empty block does not need.  The Normal output's miss value depends
     // on the direction and is not shortcut.
-    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2;
+    constexpr bool GUIDED = OUTPUT == 4;   // every statement of the guided builds sits behind this constant
+    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2 && !GUIDED;   // (a guided launch writes the Normal output too)
     if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE)
         typedef const __attribute__((address_space(4))) unsigned long long MaskK;
         if (((MaskK *)P.block_masks)[blockIdx.x] == 0ull) {
@@ -397,9 +412,29 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
     lens_begin(P, lens);
 
     // mod.rs:304-315 -> Chunk::write_* -> Buffer::write_* (buffer.rs:159-178): one sample is done
+    // Guided builds: the sample's albedo / normal / depth values are parked by the ONE event that sets have_first, straight from
+    // the registers that event holds -- nothing but the flag is carried to the end of the path (seven more live floats would
+    // cost the rect build a wave per SIMD and the volume builds spills).  A guide without a frame is neither parked nor summed;
+    // the pointers are read where they are used, through a pointer the compiler cannot see through (as the camera block is).
+    auto park_guides = [&](const V3 &albedo, const V3 &nrm, float first_t) {
+        typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
+        BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(C));
+        const size_t at = (size_t)blockIdx.x * (packed ? (size_t)P.wg_blocks << (P.log_rows + LOG_PXB) : (size_t)n_items) + park_i;
+        if (C->guide_out[0]) ((Parked *)C->guide_scratch[0])[at] = Parked{albedo.x, albedo.y, albedo.z};
+        if (C->guide_out[1]) ((Parked *)C->guide_scratch[1])[at] = Parked{nrm.x, nrm.y, nrm.z};
+        if (C->guide_out[2]) {
+            float depth = (first_t - P.clip_min) / (P.clip_max - P.clip_min);     // finish_sample's OUTPUT == 3 arithmetic
+            depth = fminf(fmaxf(depth, 0.0f), 1.0f);
+            ((Parked1 *)C->guide_scratch[2])[at] = Parked1{depth};
+        }
+    };
+    // (a path that ends without have_first parks ColorData's defaults; called next to finish_sample, not from inside it, so
+    // that the lambda below captures what it always captured)
+    auto park_guide_defaults = [&]() { park_guides(mk(0, 0, 0), mk(0, 0, 0), __builtin_inff()); };
     auto finish_sample = [&]() {
         V3 value;
-        if (OUTPUT == 0) {
+        if (OUTPUT == 0 || GUIDED) {
             value = L;
         } else if (OUTPUT == 3) {
             float depth = (first_depth - P.clip_min) / (P.clip_max - P.clip_min);
@@ -487,6 +522,7 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
                     if (OUTPUT == 1) first = mk(P.root_albedo);
                     if (OUTPUT == 2) first = P.root_has_albedo ? -rd : mk(0, 0, 0);
                     if (OUTPUT == 3) first_depth = P.root_has_albedo ? P.clip_max : __builtin_inff();
+                    if (GUIDED) park_guides(mk(P.root_albedo), P.root_has_albedo ? -rd : mk(0, 0, 0), P.root_has_albedo ? P.clip_max : __builtin_inff());
                 }
                 ended = true;
             } else {
@@ -538,11 +574,13 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
                         if (OUTPUT != 0 && !have_first) {
                             have_first = true;
                             if (OUTPUT == 1) first = mk(M.emitted);
+                            if (GUIDED) park_guides(mk(M.emitted), mk(0, 0, 0), __builtin_inff());
                         }
                         ended = true;
                     }
                 }
             }
+            if (GUIDED && ended && !have_first) park_guide_defaults();
             if (ended) finish_sample();
             if (VOTE && P.phase_vote && ev != EV_GEN) {       // in case this lane's event loses the vote below
                 held_t = h.t;
@@ -768,6 +806,7 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
                         if (OUTPUT == 1) first = mk(0.8f, 0.8f, 0.8f);
                         if (OUTPUT == 2) first = normal;
                         if (OUTPUT == 3) first_depth = hit_depth;
+                        if (GUIDED) park_guides(mk(0.8f, 0.8f, 0.8f), normal, hit_depth);
                     }
                 }                                                         // else pass through: Ray::new(pos, rd)
                 if (vol_back) {                                           // mod.rs:504-505
@@ -802,8 +841,10 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
                     if (OUTPUT == 1) first = mk(M.albedo);
                     if (OUTPUT == 2) first = normal;
                     if (OUTPUT == 3) first_depth = hit_depth;
+                    if (GUIDED) park_guides(mk(M.albedo), normal, hit_depth);
                 } else {            // ColorData::from_emitted(emitted) (mod.rs:483-485)
                     if (OUTPUT == 1) first = mk(M.emitted);
+                    if (GUIDED) park_guides(mk(M.emitted), mk(0, 0, 0), __builtin_inff());
                 }
             }
             if (scatter) {
@@ -821,6 +862,7 @@ __global__ __launch_bounds__(256, LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WA
         // the path ends before its next TRACE
         if (!late_end) late_end = (VOLS && last_object >= 0) ? (vbounce > P.max_volume_bounces) : (bounce > P.max_bounces);
         if (late_end) {
+            if (GUIDED && !have_first) park_guide_defaults();
             finish_sample();
             pending = true;
         }
@@ -893,7 +935,13 @@ queue_empty:;
             const uint32_t total = *(volatile uint32_t *)&s_segments;
             if (total) atomicAdd(&P.counters[0], (unsigned long long)total);
         }
-        sum_blocks(P, G, blockIdx.x, gridDim.x, my_blocks, T, park(), threadIdx.x, blockDim.x);
+        sum_blocks(P, G, blockIdx.x, gridDim.x, my_blocks, T, park(), threadIdx.x, blockDim.x, P.out);
+        if (GUIDED) {                                                     // each guide's plane, the same additions into its own frame
+            const size_t at = (size_t)blockIdx.x * ((size_t)P.wg_blocks << (P.log_rows + LOG_PXB));
+            if (P.guide_out[0]) sum_blocks(P, G, blockIdx.x, gridDim.x, my_blocks, T, (const Parked *)P.guide_scratch[0] + at, threadIdx.x, blockDim.x, P.guide_out[0]);
+            if (P.guide_out[1]) sum_blocks(P, G, blockIdx.x, gridDim.x, my_blocks, T, (const Parked *)P.guide_scratch[1] + at, threadIdx.x, blockDim.x, P.guide_out[1]);
+            if (P.guide_out[2]) sum_blocks(P, G, blockIdx.x, gridDim.x, my_blocks, T, (const Parked1 *)P.guide_scratch[2] + at, threadIdx.x, blockDim.x, P.guide_out[2]);
+        }
     } else {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         uint32_t arrived = 0;
@@ -905,7 +953,13 @@ queue_empty:;
                 const uint32_t total = *(volatile uint32_t *)&s_segments;
                 if (total) atomicAdd(&P.counters[0], (unsigned long long)total);
             }
-            sum_block(P, G, blockIdx.x, T, park(), lane);
+            sum_block(P, G, blockIdx.x, T, park(), lane, P.out);
+            if (GUIDED) {                                                 // each guide's plane, the same additions into its own frame
+                const size_t at = (size_t)blockIdx.x * (size_t)n_items;
+                if (P.guide_out[0]) sum_block(P, G, blockIdx.x, T, (const Parked *)P.guide_scratch[0] + at, lane, P.guide_out[0]);
+                if (P.guide_out[1]) sum_block(P, G, blockIdx.x, T, (const Parked *)P.guide_scratch[1] + at, lane, P.guide_out[1]);
+                if (P.guide_out[2]) sum_block(P, G, blockIdx.x, T, (const Parked1 *)P.guide_scratch[2] + at, lane, P.guide_out[2]);
+            }
         }
     }
     if (P.counters) {
@@ -1010,7 +1064,7 @@ extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows
 }
 // Does a launch of `P` run a build that reads BtLaunch::block_masks (the kernel's CULL)?
 extern "C" int bt_launch_reads_masks(const BtLaunch *P, int output) {
-    return !P->any_rects && !P->any_volumes && !P->lens_on && P->wg_blocks <= 1 && output != 2 && P->max_bounces >= 0;
+    return !P->any_rects && !P->any_volumes && !P->lens_on && P->wg_blocks <= 1 && output != 2 && output != 4 && P->max_bounces >= 0;
 }
 // 1: bt_api.cpp may keep a launch's masks on the scene handle; 0 (A/B variant -DBT_MASK_NOCACHE): every render computes them
 extern "C" int bt_mask_cache_enabled(void) {
@@ -1055,7 +1109,14 @@ extern "C" hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned g
 #define BT_LAUNCH_CLASS(L, K)                                                                                    \
     if (cls == 3) { BT_LAUNCH_OUT(L, true, true, K) } else if (cls == 2) { BT_LAUNCH_OUT(L, true, false, K) }      \
     else if (cls == 1) { BT_LAUNCH_OUT(L, false, true, K) } else { BT_LAUNCH_OUT(L, false, false, K) }
-    if (packed) {
+    if (output == 4) {                             // guided render (extension): no lens builds
+        if (P->lens_on) return hipErrorInvalidValue;
+#define BT_LAUNCH_GUIDED(K)                                                                                      \
+        if (cls == 3) BT_LAUNCH(4, false, true, true, K); else if (cls == 2) BT_LAUNCH(4, false, true, false, K);    \
+        else if (cls == 1) BT_LAUNCH(4, false, false, true, K); else BT_LAUNCH(4, false, false, false, K);
+        if (packed) { BT_LAUNCH_GUIDED(true) } else { BT_LAUNCH_GUIDED(false) }
+#undef BT_LAUNCH_GUIDED
+    } else if (packed) {
         BT_LAUNCH_CLASS(false, true)
     } else if (P->lens_on) {
         BT_LAUNCH_CLASS(true, false)

@@ -240,4 +240,11 @@ struct BtLaunch {
     // Sphere-only launches without volumes, lens and packing (bt_kernels.hip CULL): per block of the launch, in launch order,
     // the sphere rows its camera rays can reach (bt_cull.hpp block_mask, written by bt_block_mask_kernel); else null
     const uint64_t *block_masks;
+    // Guided render EXTENSION (not in the reference; bt_render_guided_device, the OUTPUT == 4 builds of bt_kernels.hip): the
+    // frames the first-hit albedo / normal / depth values of the colour paths are added to, [0] albedo, [1] normal, [2] depth
+    // (null = that guide is neither parked nor summed), and where each guide's values are parked -- same index as the colour
+    // value in `scratch`, 12 B per sample for albedo and normal, 4 B for the depth.  Kept at the END of the struct: the other
+    // builds never read them, and nothing they read moves.
+    float *guide_out[3];
+    float *guide_scratch[3];
 };

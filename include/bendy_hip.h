@@ -85,7 +85,8 @@ typedef struct {
                                 * workgroup through a queue; DESIGN.md 5.3 */
     uint32_t launches;         /* kernel launches the render was split into (deep renders under the scratch cap) */
     uint64_t scratch_bytes;    /* HBM the handle holds for parked sample values after this render */
-    uint64_t parked_bytes;     /* bytes of sample values the render parked in HBM (12 per sample, edge tiles padded) */
+    uint64_t parked_bytes;     /* bytes of sample values the render parked in HBM (12 per sample, edge tiles padded;
+                                * a guided render: + 12 / 12 / 4 per guide) */
     uint32_t workgroups;       /* workgroups of the last launch */
     uint32_t packed;           /* 1 / 2: the last launch was packed (bt_tuning.packed; 2 = with the compacting drain): `workgroups` = the
                                 * GPU's workgroup slots, each owning every workgroups-th pixel block behind one queue */
@@ -199,6 +200,26 @@ int bt_render(bt_scene *scene, uint64_t camera_ref, const bt_config *config, con
  * enqueues work and returns without synchronising. */
 int bt_render_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
                      float *rgba_device, uint32_t width, uint32_t height, uint64_t seed, void *stream);
+
+/* EXTENSION -- NOT IN THE REFERENCE.  One pass of Tracer::render that adds the colour samples to
+ * `color_device` and, from the same paths, the BT_OUTPUT_ALBEDO / _NORMAL / _DEPTH values to the
+ * guide frames (any of them may be NULL).  Every frame ends up bit-identical to what
+ * bt_render_device writes with the same arguments and the corresponding output: the reference fills
+ * ColorData.albedo / normal / depth in the same recursion that produces the colour (mod.rs:304-315),
+ * this entry point keeps all four -- what bt_denoise_device wants per displayed frame.
+ * Checked before the device is touched, in this order: NULL scene / config / render / colour and an
+ * effective output (render.output if has_output, else config.output) other than BT_OUTPUT_FULL ->
+ * BT_ERR_INVALID_ARG; two of the four frames being the same pointer -> BT_ERR_INVALID_ARG; a lens
+ * set on the scene -> BT_ERR_UNSUPPORTED; samples == 0 -> BT_DONE.  With all three guides NULL it is
+ * bt_render_device.  A guided sample parks 12 + 12 (albedo) + 12 (normal) + 4 (depth) bytes in the
+ * handle's scratch, so a deep render is split into more launches than the plain one
+ * (bt_tuning.scratch_cap_bytes); bt_stats.parked_bytes counts what was parked.
+ * Not provided: a host-buffer variant, a sharded variant and builds for the lens extension;
+ * bt_denoise* is unchanged. */
+int bt_render_guided_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config,
+                            const bt_render_config *render, float *color_device, float *albedo_device,
+                            float *normal_device, float *depth_device, uint32_t width, uint32_t height,
+                            uint64_t seed, void *stream);
 
 /* --- Multi-GPU pixel-tile sharding (new; the reference's only parallelism is rayon
  * tiles inside one process, tracer/mod.rs:190-197) ---------------------------------
