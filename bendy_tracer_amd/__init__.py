@@ -4,9 +4,9 @@ Only what the path needs lives here: `csrc/` (HIP kernels + scene loader + C ABI
 into `libbendy_hip.so`) and `api.py` (host-side mirror of the reference's Rust API).
 Importing the package loads the shared library; a missing library is an ImportError.
 """
-from .api import (BendyError, Buffer, ColorSpace, Comm, Config, DenoiseParams, Denoiser, Output, RenderConfig, Scene, Stats,
+from .api import (Adaptive, AdaptiveParams, AdaptiveStats, BendyError, Buffer, ColorSpace, Comm, Config, DenoiseParams, Denoiser, Output, RenderConfig, Scene, Stats,
                   Status, Subsample, Tracer, denoise, new_shard, shard_floats, tile_owner_map, unshard, write_png)
 
-__all__ = ["BendyError", "Buffer", "ColorSpace", "Comm", "Config", "DenoiseParams", "Denoiser", "Output", "RenderConfig",
+__all__ = ["Adaptive", "AdaptiveParams", "AdaptiveStats", "BendyError", "Buffer", "ColorSpace", "Comm", "Config", "DenoiseParams", "Denoiser", "Output", "RenderConfig",
            "Scene", "Stats", "Status", "Subsample", "Tracer", "denoise", "new_shard", "shard_floats", "tile_owner_map",
            "unshard", "write_png"]

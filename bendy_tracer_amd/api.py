@@ -136,6 +136,15 @@ class _CDenoiseParams(C.Structure):  # include/bendy_hip.h `bt_denoise_params` (
                 ("eps_albedo", C.c_float)]
 
 
+class _CAdaptiveParams(C.Structure):  # include/bendy_hip.h `bt_adaptive_params` (extension)
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("eps", C.c_float)]
+
+
+class AdaptiveStats(C.Structure):  # include/bendy_hip.h `bt_adaptive_stats` (extension)
+    _fields_ = [("active_tiles", C.c_uint32), ("tiles", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32),
+                ("pixel_samples", C.c_uint64), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -150,7 +159,9 @@ EXPORTS = [
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
     "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_set_object",
-    "bt_render_guided_device",
+    "bt_render_guided_device", "bt_adaptive_params_default", "bt_adaptive_new", "bt_adaptive_free", "bt_adaptive_reset",
+    "bt_render_adaptive_device", "bt_adaptive_poll", "bt_adaptive_counts", "bt_adaptive_errors", "bt_debug_adaptive_moments",
+    "bt_adaptive_resolve_device",
 ]
 
 
@@ -227,6 +238,18 @@ def _load():
                                     C.c_uint32, C.POINTER(_CDenoiseParams), vp]
     L.bt_denoise.argtypes = [vp, fp, C.c_uint32, fp, C.c_uint32, fp, C.c_uint32, fp, C.c_uint32, fp, C.c_uint32, C.c_uint32,
                              C.POINTER(_CDenoiseParams)]
+    L.bt_adaptive_params_default.argtypes = [C.POINTER(_CAdaptiveParams)]
+    L.bt_adaptive_new.restype = vp
+    L.bt_adaptive_new.argtypes = [C.c_uint32, C.c_uint32]
+    L.bt_adaptive_free.argtypes = [vp]
+    L.bt_adaptive_reset.argtypes = [vp]
+    L.bt_render_adaptive_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp,
+                                            C.POINTER(_CAdaptiveParams), vp, C.c_uint32, C.c_uint32, C.c_uint64, vp]
+    L.bt_adaptive_poll.argtypes = [vp, C.POINTER(AdaptiveStats)]
+    L.bt_adaptive_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32]
+    L.bt_adaptive_errors.argtypes = [vp, fp, C.c_uint32]
+    L.bt_debug_adaptive_moments.argtypes = [vp, fp, C.c_uint32]
+    L.bt_adaptive_resolve_device.argtypes = [vp, vp, vp, vp]
     return L
 
 
@@ -522,6 +545,27 @@ class Tracer:
                 b.inc_samples(config.samples * nn)
         return Status(rc)
 
+    def render_adaptive(self, scene: Scene, camera: int, config: RenderConfig, buffer: Buffer, adaptive: "Adaptive",
+                        seed: Optional[int] = None) -> Status:
+        """EXTENSION, not in the reference (bt_render_adaptive_device + bt_adaptive_poll): one adaptive pass
+        of `config.samples` x n^2 samples per pixel into the tiles of `buffer` that `adaptive` still holds active, then a
+        poll.  Status.Done once no tile is active.  `buffer.samples` is left alone: the tiles of an adaptively sampled
+        frame hold different numbers of samples, and the per-tile counts live on the handle (`adaptive.counts()`,
+        `adaptive.resolve(buffer)` for the mean).  The sample index continues from the handle's earlier passes.
+        A GPU buffer of the handle's size only; the effective output must be Output.Full."""
+        seed = self.DEFAULT_SEED if seed is None else seed
+        if buffer.device == "cpu":
+            raise BendyError(-1, "render_adaptive needs a device-resident buffer (there is no host-buffer variant)")
+        c, r = _c_configs(self.config, config, 0)
+        p = adaptive.params._c()
+        import torch
+        rc = _check(lib.bt_render_adaptive_device(scene._h, camera, C.byref(c), C.byref(r), adaptive._h, C.byref(p),
+                                                  buffer.data.data_ptr(), buffer.width, buffer.height, seed,
+                                                  torch.cuda.current_stream().cuda_stream))
+        if rc == Status.Done:
+            return Status.Done
+        return Status(_check(lib.bt_adaptive_poll(adaptive._h, None)))
+
     def primary_masks(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1):
         """bt_debug_primary_mask (tests): per block of a launch with `slices` blocks per tile, in launch order, the
         sphere rows a primary ray of the block may hit (uint64 bit masks)."""
@@ -669,6 +713,105 @@ class Denoiser:
             import torch
             _check(lib.bt_denoise_device(self._h, *args, out.data.data_ptr(), color.width, color.height, C.byref(cp),
                                          torch.cuda.current_stream().cuda_stream))
+        out.samples = 1
+        return out
+
+
+def _adaptive_defaults():
+    p = _CAdaptiveParams()
+    lib.bt_adaptive_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class AdaptiveParams:
+    """`bt_adaptive_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_adaptive_params_default's value."""
+    threshold: Optional[float] = None
+    min_samples: Optional[int] = None
+    max_samples: Optional[int] = None
+    eps: Optional[float] = None
+
+    def __post_init__(self):
+        d = _adaptive_defaults()
+        for k, _ in _CAdaptiveParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+
+    def _c(self):
+        return _CAdaptiveParams(float(self.threshold), int(self.min_samples), int(self.max_samples), float(self.eps))
+
+
+class Adaptive:
+    """`bt_adaptive` (include/bendy_hip.h): EXTENSION, not in the reference -- the state of variance-driven adaptive
+    sampling for one frame size: a per-pixel second moment and, per 16x16 tile, a sample count, an error
+    estimate and an activity flag.  Keywords = AdaptiveParams fields; `Tracer.render_adaptive` runs the passes."""
+
+    def __init__(self, width, height, **params):
+        self.params = AdaptiveParams(**params)
+        self.width, self.height = int(width), int(height)
+        self.tiles_x, self.tiles_y = (self.width + BT_TILE - 1) // BT_TILE, (self.height + BT_TILE - 1) // BT_TILE
+        h = lib.bt_adaptive_new(self.width, self.height)
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_adaptive_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        """Zero moments, counts and errors; every tile active again; the next pass starts at sample index 0."""
+        _check(lib.bt_adaptive_reset(self._h))
+
+    def poll(self) -> AdaptiveStats:
+        """bt_adaptive_poll (synchronises): `.active_tiles == 0` is Status.Done."""
+        st = AdaptiveStats()
+        _check(lib.bt_adaptive_poll(self._h, C.byref(st)))
+        return st
+
+    def counts(self):
+        """Samples per pixel each tile holds, uint32 [tiles_y, tiles_x]."""
+        n = _check(lib.bt_adaptive_counts(self._h, None, 0))
+        out = np.zeros(n, dtype=np.uint32)
+        _check(lib.bt_adaptive_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return out.reshape(self.tiles_y, self.tiles_x)
+
+    def errors(self):
+        """Each tile's last error estimate e_t, float32 [tiles_y, tiles_x]."""
+        n = _check(lib.bt_adaptive_errors(self._h, None, 0))
+        out = np.zeros(n, dtype=np.float32)
+        _check(lib.bt_adaptive_errors(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return out.reshape(self.tiles_y, self.tiles_x)
+
+    def moments(self):
+        """bt_debug_adaptive_moments (tests): each pixel's running sum of squared luminance, float32 [height, width]."""
+        n = _check(lib.bt_debug_adaptive_moments(self._h, None, 0))
+        out = np.zeros(n, dtype=np.float32)
+        _check(lib.bt_debug_adaptive_moments(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return out.reshape(self.height, self.width)
+
+    def resolve(self, buffer: Buffer, out: Optional[Buffer] = None) -> Buffer:
+        """The MEAN of an adaptively sampled frame: every pixel of `buffer` divided by its own tile's count.  Returns `out`
+        (a new Buffer by default) with samples = 1 and `buffer`'s color_space, as `Denoiser.denoise` does, so `.preview()`
+        and `denoise(...)` work unchanged."""
+        if buffer.device == "cpu":
+            raise BendyError(-1, "resolve needs a device-resident buffer")
+        if (buffer.width, buffer.height) != (self.width, self.height):
+            raise BendyError(-1, f"buffer of {buffer.width}x{buffer.height} on an adaptive handle of {self.width}x{self.height}")
+        if out is not None and (out is buffer or out.data is buffer.data):
+            raise BendyError(-1, "out must not be the input: the input holds running sums, out is a mean")
+        if out is None:
+            out = Buffer(buffer.width, buffer.height, buffer.color_space, device=buffer.device)
+        if (out.width, out.height) != (self.width, self.height) or out.device == "cpu":
+            raise BendyError(-1, "out must be a device-resident buffer of the handle's size")
+        out.color_space = buffer.color_space
+        import torch
+        _check(lib.bt_adaptive_resolve_device(self._h, buffer.data.data_ptr(), out.data.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream))
         out.samples = 1
         return out
 

@@ -13,6 +13,9 @@
 // albedo, normal and depth AOVs are rendered with N x subsample^2 rays per pixel (same seed) and the screenshot is the
 // denoised mean.  --denoise-inline (extension too; bt_render_guided_device): every call of the progressive loop renders the colour
 // AND the three guides in one pass into four device frames, and the screenshot is the denoised mean of those.
+// --adaptive THRESHOLD [--adaptive-min N] [--adaptive-map PATH] (extension too; bt_adaptive): every call is one adaptive pass of
+// --samples-per-call samples into the 16x16 tiles whose error estimate is still above THRESHOLD, --samples is the cap per tile,
+// the loop ends when no tile is active; the screenshot (and what --denoise filters) is the resolved mean.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -85,6 +88,10 @@ struct Args {
     bool denoise = false;
     unsigned denoise_guide_samples = 4;
     bool denoise_inline = false;
+    bool adaptive = false;
+    float adaptive_threshold = 0.0f;
+    long adaptive_min = -1;                               // -1: bt_adaptive_params_default's
+    std::string adaptive_map;
 };
 
 void usage() {
@@ -96,7 +103,10 @@ void usage() {
                  "       [--lens x,y,z,rs,step,radius[,max_steps]]   (extension: not in the reference)\n"
                  "       [--denoise] [--denoise-guide-samples 4]   (extension: not in the reference; --output full only)\n"
                  "       [--denoise-inline]   (extension: colour and guides in one pass per call; --output full only, not with\n"
-                 "                             --denoise, --shard or --lens)\n");
+                 "                             --denoise, --shard or --lens)\n"
+                 "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-map PATH]   (extension: adaptive sampling; --samples is\n"
+                 "                             the cap, --samples-per-call the pass; --output full only, not with --lens, --shard\n"
+                 "                             or --denoise-inline)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -144,6 +154,16 @@ Args parse(int argc, char **argv) {
         else if (k == "--denoise") a.denoise = true;
         else if (k == "--denoise-inline") a.denoise_inline = true;
         else if (k == "--denoise-guide-samples") a.denoise_guide_samples = (unsigned)std::strtoul(val().c_str(), nullptr, 10);
+        else if (k == "--adaptive") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.adaptive_threshold = std::strtof(spec.c_str(), &end);
+            if (spec.empty() || *end != 0 || !(a.adaptive_threshold >= 0.0f) || !(a.adaptive_threshold < 3.0e38f))
+                die("--adaptive expects a finite threshold >= 0");
+            a.adaptive = true;
+        }
+        else if (k == "--adaptive-min") a.adaptive_min = (long)std::strtoul(val().c_str(), nullptr, 10);
+        else if (k == "--adaptive-map") a.adaptive_map = val();
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -156,6 +176,12 @@ Args parse(int argc, char **argv) {
     if (a.denoise_inline && a.denoise) die("--denoise-inline and --denoise exclude each other");
     if (a.denoise_inline && a.shard_world > 1) die("--denoise-inline does not apply to a --shard run");
     if (a.denoise_inline && a.has_lens) die("--denoise-inline has no builds for --lens");
+    if (!a.adaptive && (a.adaptive_min >= 0 || !a.adaptive_map.empty())) die("--adaptive-min and --adaptive-map need --adaptive");
+    if (a.adaptive && a.output != "full") die("--adaptive needs --output full");
+    if (a.adaptive && a.has_lens) die("--adaptive has no builds for --lens");
+    if (a.adaptive && a.shard_world > 1) die("--adaptive does not apply to a --shard run");
+    if (a.adaptive && a.denoise_inline) die("--adaptive has no guided variant: use --denoise, not --denoise-inline");
+    if (a.adaptive && a.adaptive_min > (long)a.samples) die("--adaptive-min must not exceed --samples (the cap)");
     return a;
 }
 
@@ -233,7 +259,46 @@ int main(int argc, char **argv) {
     double sum_delta = 0.0;
     const auto start = std::chrono::steady_clock::now();
     std::string per_call;                                  // --stats-json rows
-    while (buffer_samples < args.samples) {
+    // --adaptive (extension): passes of samples_per_call samples into the tiles still active, until none is
+    bt_adaptive *adaptive = nullptr;
+    bt_adaptive_stats astats{};
+    float *d_mean = nullptr;                               // the resolved mean
+    if (args.adaptive) {
+        adaptive = bt_adaptive_new(args.width, args.height);
+        if (!adaptive) die(bt_last_error());
+        bt_adaptive_params ap;
+        bt_adaptive_params_default(&ap);
+        ap.threshold = args.adaptive_threshold;
+        ap.max_samples = args.samples;
+        ap.min_samples = args.adaptive_min >= 0 ? (uint32_t)args.adaptive_min : std::min(ap.min_samples, ap.max_samples);
+        rc.samples = args.samples_per_call;
+        for (;;) {
+            const auto t0 = std::chrono::steady_clock::now();
+            check(bt_render_adaptive_device(scene, camera, &cfg, &rc, adaptive, &ap, d_frame, args.width, args.height, args.seed, nullptr),
+                  "bt_render_adaptive_device");
+            const int st = bt_adaptive_poll(adaptive, &astats);
+            check(st, "bt_adaptive_poll");
+            const double delta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            sum_delta += delta;
+            buffer_samples = astats.max_count;
+            if (!args.stats_json.empty()) {
+                bt_stats cs{};
+                bt_scene_last_stats(scene, &cs);
+                char row[256];
+                std::snprintf(row, sizeof row, "%s{\"kernel_ms\": %.5f, \"segments\": %llu, \"active_tiles\": %u, \"slices\": %u, \"packed\": %u}",
+                              per_call.empty() ? "" : ", ", cs.kernel_ms, (unsigned long long)cs.segments, astats.active_tiles, cs.slices, cs.packed);
+                per_call += row;
+            }
+            if (!args.quiet)
+                std::fprintf(stderr, "bendy tracer; adaptive pass %u; samples: %u..%u/%u; active tiles: %u/%u; delta t: %s\n", astats.passes,
+                             astats.min_count, astats.max_count, args.samples, astats.active_tiles, astats.tiles, fmt_duration(delta).c_str());
+            if (st == BT_DONE) break;
+        }
+        hip_check(hipMalloc((void **)&d_mean, n_px * 16), "hipMalloc");
+        check(bt_adaptive_resolve_device(adaptive, d_frame, d_mean, nullptr), "bt_adaptive_resolve_device");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    }
+    while (!args.adaptive && buffer_samples < args.samples) {
         rc.samples = std::min(args.samples_per_call, std::max(1u, (args.samples - buffer_samples) / nn));
         rc.sample_base = (buffer_samples + nn - 1) / nn;
         const auto t0 = std::chrono::steady_clock::now();
@@ -266,14 +331,23 @@ int main(int argc, char **argv) {
     bt_scene_last_stats(scene, &stats);
     std::fprintf(stderr, "bendy tracer; samples: %u/%u; avg t per sample: %s; total t: %s\n", buffer_samples, args.samples,
                  fmt_duration(buffer_samples ? sum_delta / buffer_samples : 0.0).c_str(), fmt_duration(total).c_str());
+    if (args.adaptive)
+        std::fprintf(stderr, "%.1f Msamples/s (adaptive passes: %llu pixel-samples in %u passes, %u..%u samples per tile)\n",
+                     sum_delta > 0 ? (double)astats.pixel_samples / sum_delta / 1e6 : 0.0, (unsigned long long)astats.pixel_samples,
+                     astats.passes, astats.min_count, astats.max_count);
+    else
     std::fprintf(stderr, "%.1f Msamples/s (render calls only)\n",
                  sum_delta > 0 ? (double)n_px * buffer_samples / sum_delta / 1e6 : 0.0);
 
     if (!args.stats_json.empty()) {
         FILE *f = std::fopen(args.stats_json.c_str(), "w");
         if (!f) die("cannot write " + args.stats_json);
-        std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str());
+        char ad[320] = "";
+        if (args.adaptive)
+            std::snprintf(ad, sizeof ad, ", \"adaptive\": {\"active_tiles\": %u, \"tiles\": %u, \"min_count\": %u, \"max_count\": %u, \"pixel_samples\": %llu, \"passes\": %u}",
+                          astats.active_tiles, astats.tiles, astats.min_count, astats.max_count, (unsigned long long)astats.pixel_samples, astats.passes);
+        std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s}\n", args.width,
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad);
         std::fclose(f);
     }
 
@@ -297,6 +371,24 @@ int main(int argc, char **argv) {
     // --denoise (extension): the guides of the same frame into fresh buffers, then the screenshot shows the denoised mean
     float *d_shown = d_frame;
     unsigned shown_samples = buffer_samples ? buffer_samples : 1;
+    if (args.adaptive) {                                    // everything below sees the resolved mean
+        d_shown = d_mean;
+        shown_samples = 1;
+        if (!args.adaptive_map.empty()) {
+            // the per-tile counts as a grey image, one pixel per tile, 255 = the cap
+            std::vector<uint32_t> counts((size_t)astats.tiles);
+            check(bt_adaptive_counts(adaptive, counts.data(), astats.tiles), "bt_adaptive_counts");
+            const unsigned tx = (args.width + BT_TILE - 1) / BT_TILE, ty = (args.height + BT_TILE - 1) / BT_TILE;
+            std::vector<uint8_t> grey((size_t)tx * ty * 4);
+            for (size_t t = 0; t < counts.size(); ++t) {
+                const uint8_t v = (uint8_t)std::min<uint64_t>(255, (uint64_t)counts[t] * 255 / std::max(1u, args.samples));
+                grey[4 * t] = grey[4 * t + 1] = grey[4 * t + 2] = v;
+                grey[4 * t + 3] = 255;
+            }
+            check(bt_write_png(args.adaptive_map.c_str(), grey.data(), tx, ty), "bt_write_png (--adaptive-map)");
+            std::fprintf(stderr, "saved count map to %s\n", args.adaptive_map.c_str());
+        }
+    }
     if (args.denoise_inline && !args.no_screenshot) {
         bt_denoiser *dn = bt_denoiser_new();
         check(bt_denoise_device(dn, d_frame, shown_samples, d_guides[0], shown_samples, d_guides[1], shown_samples, d_guides[2],
@@ -325,7 +417,7 @@ int main(int argc, char **argv) {
         }
         const uint32_t gs = args.denoise_guide_samples * nn;
         bt_denoiser *dn = bt_denoiser_new();
-        check(bt_denoise_device(dn, d_frame, shown_samples, d_guides[0], gs, d_guides[1], gs, d_guides[2], gs, d_guides[3],
+        check(bt_denoise_device(dn, d_shown, shown_samples, d_guides[0], gs, d_guides[1], gs, d_guides[2], gs, d_guides[3],
                                 args.width, args.height, nullptr, nullptr),
               "bt_denoise_device");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
@@ -351,6 +443,8 @@ int main(int argc, char **argv) {
 
     (void)hipFree(d_frame);
     (void)hipFree(d_rgba8);
+    if (d_mean) (void)hipFree(d_mean);
+    bt_adaptive_free(adaptive);
     for (float *g : d_guides)
         if (g) (void)hipFree(g);
     bt_scene_free(scene);

@@ -393,9 +393,12 @@ int fill_launch(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const bt
 
 // `guides` (bt_render_guided_device, an extension): null, or the albedo / normal / depth frames of a guided render, any of them
 // null; the caller has checked that the effective output is BT_OUTPUT_FULL and that no lens is set.
+// `adapt` (bt_render_adaptive_device, an extension; bt_adapt_api.cpp): null, or the per-tile activity flags and the moment plane
+// of one adaptive pass -- the OUTPUT == 5 builds, never packed; the caller has checked the same two things.
+struct AdaptPass { const uint32_t *tile_active; float *moment; };
 int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const bt_render_config *rc, float *out_device,
                   uint32_t width, uint32_t height, uint32_t rank, uint32_t world, bool sharded, uint64_t seed,
-                  hipStream_t stream, float *const *guides = nullptr) {
+                  hipStream_t stream, float *const *guides = nullptr, const AdaptPass *adapt = nullptr) {
     if (!s || !cfg || !rc || !out_device) return set_error(BT_ERR_INVALID_ARG, "null argument");
     if (rc->samples == 0) return BT_DONE;                              // mod.rs:186-188
     if (world == 0 || rank >= world) return set_error(BT_ERR_INVALID_ARG, "rank/world out of range");
@@ -419,6 +422,11 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
             P.guide_out[g] = guides[g];
             if (guides[g]) sample_bytes += (g == 2 ? 1 : 3) * sizeof(float);
         }
+    }
+    if (adapt) {
+        output = 5;
+        P.tile_active = adapt->tile_active;
+        P.moment = adapt->moment;
     }
     const uint32_t n_tiles = P.tiles_x * P.tiles_y;
     const uint32_t grid = sharded ? (n_tiles + world - 1) / world : n_tiles;
@@ -549,7 +557,7 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
     // their drains with other workgroups' work and lose 5 - 20 % when packed, emptier ones do not fill the slots
     const uint64_t items_all = px_launch * T_launch, lanes_all = (uint64_t)wg_slots * 256;
     const bool pack = tune.packed > 0 || (tune.packed < 0 && items_all > lanes_all && items_all <= 24 * lanes_all);
-    if (pack && chunk == (uint32_t)P.samples && !P.lens_on) {                     // (the lens extension has no packed builds)
+    if (pack && chunk == (uint32_t)P.samples && !P.lens_on && !adapt) {           // (the lens extension and the adaptive pass have no packed builds)
         // blocks of ~64 / T pixels: one wave's take from the queue is one block's samples (coherent camera rays)
         uint32_t S = 4;
         while (S < 32 && S < 4 * T_launch) S *= 2;
@@ -936,6 +944,16 @@ int bt_render_device(bt_scene *scene, uint64_t camera_ref, const bt_config *conf
     return render_common(scene, camera_ref, config, render, rgba_device, width, height, 0, 1, false, seed,
                          (hipStream_t)stream);
 }
+
+// The render half of bt_render_adaptive_device (bt_adapt_api.cpp, which has validated everything); not in the header.
+int bt_render_adaptive_pass_internal(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                                     float *rgba_device, uint32_t width, uint32_t height, uint64_t seed, void *stream,
+                                     const uint32_t *tile_active, float *moment) {
+    const AdaptPass pass{tile_active, moment};
+    return render_common(scene, camera_ref, config, render, rgba_device, width, height, 0, 1, false, seed, (hipStream_t)stream,
+                         nullptr, &pass);
+}
+int bt_scene_lens_on_internal(const bt_scene *scene) { return scene && scene->lens_on ? 1 : 0; }   // for bt_adapt_api.cpp; not in the header
 
 int bt_render_guided_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
                             float *color_device, float *albedo_device, float *normal_device, float *depth_device,

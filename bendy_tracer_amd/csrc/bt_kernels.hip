@@ -101,12 +101,21 @@ BT_DEV float *out_of(const BtLaunch &P, float *frame, const BlockRef &B, const P
                      : frame + ((size_t)r.py * P.width + r.px) * 4;
 }
 
+// Adaptive sampling (EXTENSION, OUTPUT == 5): a sample's contribution to its pixel's second moment -- the square of its
+// Rec. 709 luminance, added in sample order next to the colour (bt_adapt.hip turns sum and moment into the tile's error)
+BT_DEV float moment_add(float m, const V3 &v) {
+    const float Y = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z;
+    return m + Y * Y;
+}
+
 // `*r += pixel.r` (buffer.rs:159-164) for every parked sample of block b's pixels, in sample order -- the additions a
 // lane that owned the pixel would perform in a register, in the same order, hence the same bits.  Executed by ONE wave
 // (`lane` = 0 .. 63); src = the block's parked values, src[k * pxb + pixel].
 // PK = Parked, or Parked1 for the depth plane of a guided render; `frame` = the frame the plane is added to.
-template <class PK>
-BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_t T, const PK *src, uint32_t lane, float *frame) {
+// MOMENT (adaptive builds): the wave also adds every value's squared luminance to moment[py * width + px], in the same order.
+template <class PK, bool MOMENT = false>
+BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_t T, const PK *src, uint32_t lane, float *frame,
+                      float *moment = nullptr) {
     const BlockRef B = block_ref(P, g, b);
     const uint32_t pxb = g.pxb;
     if (pxb >= 64) {
@@ -116,21 +125,32 @@ BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_
             float *o = out_of(P, frame, B, r);
             const PK *s = src + q;
             V3 sum = mk(o[0], o[1], o[2]);
+            float *mo = nullptr;
+            float m = 0.0f;
+            if constexpr (MOMENT) {
+                mo = moment + ((size_t)r.py * P.width + r.px);
+                m = *mo;
+            }
             uint32_t kk = 0;
             for (; kk + BT_SUM_BATCH <= T; kk += BT_SUM_BATCH) {   // BT_SUM_BATCH loads in flight, additions strictly in order
                 PK v[BT_SUM_BATCH];
 #pragma unroll
                 for (int j = 0; j < BT_SUM_BATCH; ++j) v[j] = s[(size_t)(kk + j) * pxb];
 #pragma unroll
-                for (int j = 0; j < BT_SUM_BATCH; ++j) sum = sum + v3_of(v[j]);
+                for (int j = 0; j < BT_SUM_BATCH; ++j) {
+                    sum = sum + v3_of(v[j]);
+                    if constexpr (MOMENT) m = moment_add(m, v3_of(v[j]));
+                }
             }
             for (; kk < T; ++kk) {
                 const PK v = s[(size_t)kk * pxb];
                 sum = sum + v3_of(v);
+                if constexpr (MOMENT) m = moment_add(m, v3_of(v));
             }
             o[0] = sum.x;
             o[1] = sum.y;
             o[2] = sum.z;
+            if constexpr (MOMENT) *mo = m;
         }
     } else {
         // 32, 16 or 8 pixels (deep launches, T in the hundreds): J = 64 / pxb lanes per pixel fetch interleaved
@@ -142,6 +162,12 @@ BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_
         const PK *s = src + q;
         V3 sum = mk(0.0f, 0.0f, 0.0f);
         if (owner) sum = mk(o[0], o[1], o[2]);
+        float *mo = nullptr;
+        float m = 0.0f;
+        if constexpr (MOMENT) {
+            mo = moment + ((size_t)r.py * P.width + r.px);
+            if (owner) m = *mo;
+        }
         for (uint32_t kk = 0; kk < T; kk += 8 * J) {
             PK v[8];
 #pragma unroll
@@ -154,13 +180,17 @@ BT_DEV void sum_block(const BtLaunch &P, const BlockGeom &g, uint32_t b, uint32_
                 for (uint32_t jj = 0; jj < J; ++jj) {
                     const int from = (int)(q + jj * pxb);
                     const V3 val = shfl_v3(v[u], from);
-                    if (kk + (uint32_t)u * J + jj < T) sum = sum + val;
+                    if (kk + (uint32_t)u * J + jj < T) {
+                        sum = sum + val;
+                        if constexpr (MOMENT) m = moment_add(m, val);
+                    }
                 }
         }
         if (owner) {
             o[0] = sum.x;
             o[1] = sum.y;
             o[2] = sum.z;
+            if constexpr (MOMENT) *mo = m;
         }
     }
 }
@@ -245,7 +275,9 @@ __global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t
 
 // --------------------------------------------------------------------------------------------
 // The render kernel.  OUTPUT: 0 Full, 1 Albedo, 2 Normal, 3 Depth (tracer/mod.rs:108-115); 4 = Full plus the three others
-// from the same paths, each into a frame of its own (guided render, an EXTENSION: bt_render_guided_device).
+// from the same paths, each into a frame of its own (guided render, an EXTENSION: bt_render_guided_device);
+// 5 = Full into the tiles that BtLaunch::tile_active marks, plus each pixel's second moment (adaptive sampling, an EXTENSION:
+// bt_render_adaptive_device; LENS = PACKED = false only).
 // Block = 256 threads; 7 waves per SIMD caps the allocation at 72 VGPRs (round 2, without the SLP vectorizer;
 // profiles/r03c/ab_waves_noslp.log, ab_waves_per_class.log).
 #ifndef BT_WAVES_PER_SIMD
@@ -281,7 +313,21 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
     // ahead of the LDS staging and its barrier, which an empty block does not need.  The Normal output's miss value depends
     // on the direction and is not shortcut.
     constexpr bool GUIDED = OUTPUT == 4;   // every statement of the guided builds sits behind this constant
-    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2 && !GUIDED;   // (a guided launch writes the Normal output too)
+    constexpr bool ADAPT = OUTPUT == 5;    // ... and every statement of the adaptive builds behind this one
+    constexpr bool AOV = OUTPUT != 0 && !ADAPT;    // the build keeps a path's first hit (the adaptive builds are Full builds)
+    constexpr bool CULL = !LENS && !RECTS && !VOLS && !PACKED && OUTPUT != 2 && !GUIDED && !ADAPT;   // (a guided launch writes the Normal output too)
+    // ---- adaptive sampling: a tile that has converged ----
+    // bt_adapt_update_kernel has cleared tile_active[tile] once the tile's error estimate fell below the threshold: one
+    // wave-uniform (scalar) load ahead of the LDS staging, as the empty-block test below, and read through the same opaque
+    // pointer so that nothing of it stays in SGPRs.  The tile's pixels, moments and the segment counter stay untouched.
+    if (ADAPT) {
+        typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
+        typedef const __attribute__((address_space(4))) uint32_t ActiveK;
+        BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(C));
+        const uint32_t slot = blockIdx.x >> (uint32_t)__builtin_ctz((uint32_t)C->slices);
+        if (((ActiveK *)C->tile_active)[slot] == 0u) return;
+    }
     if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE)
         typedef const __attribute__((address_space(4))) unsigned long long MaskK;
         if (((MaskK *)P.block_masks)[blockIdx.x] == 0ull) {
@@ -434,7 +480,7 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
     auto park_guide_defaults = [&]() { park_guides(mk(0, 0, 0), mk(0, 0, 0), __builtin_inff()); };
     auto finish_sample = [&]() {
         V3 value;
-        if (OUTPUT == 0 || GUIDED) {
+        if (OUTPUT == 0 || GUIDED || ADAPT) {
             value = L;
         } else if (OUTPUT == 3) {
             float depth = (first_depth - P.clip_min) / (P.clip_max - P.clip_min);
@@ -517,7 +563,7 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
             } else if (h.prim < 0) {
                 // sample_root (mod.rs:429-452)
                 L = L + beta * mk(P.root_color);
-                if (OUTPUT != 0 && !have_first) {
+                if (AOV && !have_first) {
                     have_first = true;
                     if (OUTPUT == 1) first = mk(P.root_albedo);
                     if (OUTPUT == 2) first = P.root_has_albedo ? -rd : mk(0, 0, 0);
@@ -571,7 +617,7 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
                     else if (M.kind == BT_MAT_GLASS) ev = EV_GLASS;
                     else {
                         // Flat / Emissive: no scatter -> ColorData::from_emitted (mod.rs:483-485)
-                        if (OUTPUT != 0 && !have_first) {
+                        if (AOV && !have_first) {
                             have_first = true;
                             if (OUTPUT == 1) first = mk(M.emitted);
                             if (GUIDED) park_guides(mk(M.emitted), mk(0, 0, 0), __builtin_inff());
@@ -801,7 +847,7 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
                     if (inside) new_o = pos - (rd * P.volume_step) * u24(u.y);
                     dir = v;
                     beta = beta * mk(0.8f, 0.8f, 0.8f);
-                    if (OUTPUT != 0 && !have_first) {
+                    if (AOV && !have_first) {
                         have_first = true;
                         if (OUTPUT == 1) first = mk(0.8f, 0.8f, 0.8f);
                         if (OUTPUT == 2) first = normal;
@@ -835,7 +881,7 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
                 scatter = !(fabsf(p) <= 1e-5f);                           // Pdf::pdf (:279-286)
                 weight = pd / p;                                          // Material::pdf (:204) / shade.pdf
             }
-            if (OUTPUT != 0 && !have_first) {
+            if (AOV && !have_first) {
                 have_first = true;
                 if (scatter) {      // data.albedo ColorData (material.rs:99-104,140-145,169-174)
                     if (OUTPUT == 1) first = mk(M.albedo);
@@ -953,7 +999,15 @@ queue_empty:;
                 const uint32_t total = *(volatile uint32_t *)&s_segments;
                 if (total) atomicAdd(&P.counters[0], (unsigned long long)total);
             }
-            sum_block(P, G, blockIdx.x, T, park(), lane, P.out);
+            if constexpr (ADAPT) {
+                // the moment plane's address is read here, behind the loop, through the opaque pointer (see the prologue)
+                typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
+                BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
+                asm volatile("" : "+s"(C));
+                sum_block<Parked, true>(P, G, blockIdx.x, T, park(), lane, P.out, C->moment);
+            } else {
+                sum_block(P, G, blockIdx.x, T, park(), lane, P.out);
+            }
             if (GUIDED) {                                                 // each guide's plane, the same additions into its own frame
                 const size_t at = (size_t)blockIdx.x * (size_t)n_items;
                 if (P.guide_out[0]) sum_block(P, G, blockIdx.x, T, (const Parked *)P.guide_scratch[0] + at, lane, P.guide_out[0]);
@@ -1064,7 +1118,7 @@ extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows
 }
 // Does a launch of `P` run a build that reads BtLaunch::block_masks (the kernel's CULL)?
 extern "C" int bt_launch_reads_masks(const BtLaunch *P, int output) {
-    return !P->any_rects && !P->any_volumes && !P->lens_on && P->wg_blocks <= 1 && output != 2 && output != 4 && P->max_bounces >= 0;
+    return !P->any_rects && !P->any_volumes && !P->lens_on && P->wg_blocks <= 1 && output != 2 && output != 4 && output != 5 && P->max_bounces >= 0;
 }
 // 1: bt_api.cpp may keep a launch's masks on the scene handle; 0 (A/B variant -DBT_MASK_NOCACHE): every render computes them
 extern "C" int bt_mask_cache_enabled(void) {
@@ -1109,7 +1163,11 @@ extern "C" hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned g
 #define BT_LAUNCH_CLASS(L, K)                                                                                    \
     if (cls == 3) { BT_LAUNCH_OUT(L, true, true, K) } else if (cls == 2) { BT_LAUNCH_OUT(L, true, false, K) }      \
     else if (cls == 1) { BT_LAUNCH_OUT(L, false, true, K) } else { BT_LAUNCH_OUT(L, false, false, K) }
-    if (output == 4) {                             // guided render (extension): no lens builds
+    if (output == 5) {                             // adaptive pass (extension): four builds, neither lens nor packed
+        if (P->lens_on || packed || !P->tile_active || !P->moment) return hipErrorInvalidValue;
+        if (cls == 3) BT_LAUNCH(5, false, true, true, false); else if (cls == 2) BT_LAUNCH(5, false, true, false, false);
+        else if (cls == 1) BT_LAUNCH(5, false, false, true, false); else BT_LAUNCH(5, false, false, false, false);
+    } else if (output == 4) {                      // guided render (extension): no lens builds
         if (P->lens_on) return hipErrorInvalidValue;
 #define BT_LAUNCH_GUIDED(K)                                                                                      \
         if (cls == 3) BT_LAUNCH(4, false, true, true, K); else if (cls == 2) BT_LAUNCH(4, false, true, false, K);    \

@@ -247,4 +247,10 @@ struct BtLaunch {
     // builds never read them, and nothing they read moves.
     float *guide_out[3];
     float *guide_scratch[3];
+    // Adaptive sampling EXTENSION (not in the reference; bt_render_adaptive_device, the OUTPUT == 5 builds of bt_kernels.hip):
+    // tile_active[slot] == 0: the tile has converged, its workgroups return at once; moment[py * width + px] = the running sum
+    // of the squared luminance of the pixel's samples (row-major, 4 B per pixel; bt_adapt.hip reads it).  Behind the guides'
+    // fields for the same reason: no other build reads them.
+    const uint32_t *tile_active;
+    float *moment;
 };

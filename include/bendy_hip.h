@@ -298,6 +298,68 @@ int bt_denoise(bt_denoiser *d, const float *color, uint32_t color_samples,
                const float *depth, uint32_t depth_samples,
                float *out, uint32_t width, uint32_t height, const bt_denoise_params *params);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: variance-driven adaptive sampling -------------------------
+ * bendy-tracer v1 spends the same number of samples on every pixel.  This mode is off unless called and changes no
+ * other entry point.  A bt_adaptive handle keeps, for one frame size, a per-pixel second moment (the running sum of
+ * the squared Rec. 709 luminance of the pixel's samples, 4 B per pixel) and per 16x16 tile a sample count, an error
+ * estimate and an activity flag.  One pass (bt_render_adaptive_device) adds render.samples * n^2 samples per pixel to
+ * the tiles that are still active -- the paths, Philox blocks and additions of bt_render_device, so a tile with
+ * count c holds bit for bit what bt_render_device gives its pixels for the sample indices [0, c / n^2) -- and then
+ * re-estimates every active tile.  With T = samples * n^2, c = the tile's count after the pass, (r, g, b) a pixel's
+ * colour sum and M its moment, all in float32:
+ *     S = (0.2126 r + 0.7152 g) + 0.0722 b;  mu = S / c;  var = max(0, M / c - mu * mu);
+ *     e_p = sqrt(var / c) / (mu + eps), a non-finite e_p counting as 0;
+ *     e_t = the mean of e_p over the tile's pixels inside the frame;
+ *     the tile stops when c >= max_samples, or when c >= min_samples and e_t <= threshold; it never starts again.
+ * Counts are in samples per pixel (n^2 per subsampled sample), as Buffer::samples is. */
+typedef struct {
+    float threshold;           /* >= 0, finite: a tile stops once its relative standard error e_t is at or below it */
+    uint32_t min_samples;      /* samples per pixel every tile gets before it may stop on its error */
+    uint32_t max_samples;      /* >= min_samples: samples per pixel at which a tile stops whatever its error */
+    float eps;                 /* added to the mean luminance in e_p's denominator */
+} bt_adaptive_params;
+typedef struct {
+    uint32_t active_tiles;     /* tiles the next pass would sample */
+    uint32_t tiles;
+    uint32_t min_count, max_count;   /* smallest / largest per-tile count */
+    uint64_t pixel_samples;    /* samples taken so far, summed over the frame's pixels */
+    uint32_t passes;           /* passes since bt_adaptive_reset */
+    uint32_t reserved;
+} bt_adaptive_stats;
+typedef struct bt_adaptive bt_adaptive;   /* owns moment plane, counts, flags, errors; one frame size, one stream at a time */
+void bt_adaptive_params_default(bt_adaptive_params *out);
+/* No device work happens here: the buffers are allocated by the first pass, on the device current then.  NULL for a
+ * zero-sized frame. */
+bt_adaptive *bt_adaptive_new(uint32_t width, uint32_t height);
+void bt_adaptive_free(bt_adaptive *a);
+/* Zero moments, counts and errors, every tile active, next sample index 0, the pass size forgotten. */
+int bt_adaptive_reset(bt_adaptive *a);
+/* One asynchronous pass on `stream` into `rgba_device` (the frame of running sums, row-major RGBA32F, which must hold
+ * the sums of the handle's earlier passes since the reset -- zero + alpha for a fresh frame).  render.sample_base is
+ * ignored: the handle's next sample index is used.  Never a packed launch; shares the scene handle's scratch, split
+ * launches and pinned slices with bt_render_device.  Checked before the device is touched, in this order: NULL scene /
+ * config / render / adaptive / params / rgba -> BT_ERR_INVALID_ARG; an effective output other than BT_OUTPUT_FULL ->
+ * BT_ERR_INVALID_ARG; width, height other than the handle's -> BT_ERR_INVALID_ARG; threshold negative or not finite
+ * -> BT_ERR_INVALID_ARG; min_samples > max_samples -> BT_ERR_INVALID_ARG; samples or subsample_n other than those
+ * of the handle's earlier passes since the reset -> BT_ERR_INVALID_ARG; a lens set on the scene -> BT_ERR_UNSUPPORTED;
+ * samples == 0 -> BT_DONE.  Returns BT_DONE as well (nothing is launched) once a poll has found no tile active, else
+ * BT_IN_PROGRESS.  bt_scene_last_stats afterwards: `samples` counts every tile as if it were active.
+ * Not provided: guided, sharded, host-buffer, lens and packed variants, and a finer granularity than the tile. */
+int bt_render_adaptive_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                              bt_adaptive *adaptive, const bt_adaptive_params *params, float *rgba_device, uint32_t width,
+                              uint32_t height, uint64_t seed, void *stream);
+/* Waits for the stream of the last pass; BT_DONE when no tile is active any more, else BT_IN_PROGRESS.  `out` may be NULL. */
+int bt_adaptive_poll(bt_adaptive *a, bt_adaptive_stats *out);
+/* Per-tile counts / error estimates (tiles row-major, tiles_x = ceil(width / 16)) and, for tests, the per-pixel moment
+ * plane (row-major): n == 0 returns the number of elements, else up to n are copied to `host` (synchronises) and the
+ * number copied is returned. */
+int bt_adaptive_counts(bt_adaptive *a, uint32_t *host, uint32_t n);
+int bt_adaptive_errors(bt_adaptive *a, float *host, uint32_t n);
+int bt_debug_adaptive_moments(bt_adaptive *a, float *host, uint32_t n);
+/* out.rgb = rgba.rgb * (1 / the pixel's tile's count), 0 for a count of 0; out.a = rgba.a: the MEAN, to be previewed
+ * with samples = 1 or handed to bt_denoise_device with color_samples = 1.  `out` must not be `rgba`. */
+int bt_adaptive_resolve_device(bt_adaptive *a, const float *rgba_device, float *out_device, void *stream);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);
