@@ -159,6 +159,7 @@ EXPORTS = [
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
     "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_set_object",
+    "bt_debug_plan_launch",
     "bt_render_guided_device", "bt_adaptive_params_default", "bt_adaptive_new", "bt_adaptive_free", "bt_adaptive_reset",
     "bt_render_adaptive_device", "bt_adaptive_poll", "bt_adaptive_counts", "bt_adaptive_errors", "bt_debug_adaptive_moments",
     "bt_adaptive_resolve_device",
@@ -205,6 +206,9 @@ def _load():
     L.bt_debug_block_masks_device.argtypes = L.bt_debug_primary_mask.argtypes
     L.bt_debug_mask_key.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32]
+    L.bt_debug_plan_launch.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
+                                       C.POINTER(Stats)]
     L.bt_render.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), fp, C.c_uint32,
                             C.c_uint32, C.c_uint64]
     L.bt_render_device.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), vp, C.c_uint32,
@@ -594,6 +598,17 @@ class Tracer:
         out = (C.c_uint8 * n)()
         _check(lib.bt_debug_mask_key(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world, out, n))
         return bytes(out)
+
+    def plan_launch(self, scene: Scene, camera: int, config: RenderConfig, width, height, n_cu, rank=0, world=1, sharded=False,
+                    kind=0, guides=0, alloc_limit=0) -> Stats:
+        """bt_debug_plan_launch (tests): the launch-shape fields of the bt_stats a render of these arguments would leave on a
+        device of `n_cu` compute units, planned without a GPU.  kind: 0 plain, 1 guided (`guides`: bit mask of the guides
+        present), 2 adaptive; allocations above `alloc_limit` bytes fail (0: none does)."""
+        c, r = _c_configs(self.config, config, 0)
+        st = Stats()
+        _check(lib.bt_debug_plan_launch(scene._h, camera, C.byref(c), C.byref(r), width, height, rank, world, int(sharded),
+                                        n_cu, kind, guides, alloc_limit, C.byref(st)))
+        return st
 
     # ---- multi-GPU tile sharding (DESIGN.md "Multi-GPU") ----
     def render_shard(self, scene: Scene, camera: int, config: RenderConfig, shard, width, height, rank, world,

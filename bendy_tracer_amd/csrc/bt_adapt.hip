@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/bendy_hip.h"
+#include "bt_internal.hpp"
 
 namespace {
 constexpr uint32_t TILE = BT_TILE;

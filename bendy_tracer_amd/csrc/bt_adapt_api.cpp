@@ -9,28 +9,8 @@
 #include <vector>
 
 #include "../../include/bendy_hip.h"
-
-extern "C" int bt_set_error_internal(int code, const char *msg);      // bt_api.cpp
-extern "C" int bt_scene_lens_on_internal(const bt_scene *scene);
-extern "C" int bt_render_adaptive_pass_internal(bt_scene *scene, uint64_t camera_ref, const bt_config *config,
-                                                const bt_render_config *render, float *rgba_device, uint32_t width,
-                                                uint32_t height, uint64_t seed, void *stream, const uint32_t *tile_active,
-                                                float *moment);
-extern "C" hipError_t bt_launch_adapt_update(const float *rgba, const float *moment, uint32_t *count, uint32_t *active,
-                                             float *error, uint32_t *n_active, uint32_t width, uint32_t height, uint32_t T,
-                                             const bt_adaptive_params *p, hipStream_t stream);
-extern "C" hipError_t bt_launch_adapt_resolve(const float *rgba, const uint32_t *count, float *out, uint32_t width,
-                                              uint32_t height, hipStream_t stream);
-
-namespace {
-int fail(int code, const std::string &msg) { return bt_set_error_internal(code, msg.c_str()); }
-int hip_fail(const char *what, hipError_t e) { return fail(BT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-#define BT_HIP(expr)                                        \
-    do {                                                    \
-        hipError_t _e = (expr);                             \
-        if (_e != hipSuccess) return hip_fail(#expr, _e);   \
-    } while (0)
-} // namespace
+#include "bt_internal.hpp"
+#include "bt_plan.hpp"
 
 struct bt_adaptive {
     uint32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0;
@@ -119,8 +99,8 @@ bt_adaptive *bt_adaptive_new(uint32_t width, uint32_t height) {
     bt_adaptive *a = new bt_adaptive();
     a->width = width;
     a->height = height;
-    a->tiles_x = (width + BT_TILE - 1) / BT_TILE;
-    a->tiles_y = (height + BT_TILE - 1) / BT_TILE;
+    a->tiles_x = btplan::tiles_across(width);
+    a->tiles_y = btplan::tiles_across(height);
     return a;
 }
 
@@ -195,11 +175,7 @@ int bt_adaptive_poll(bt_adaptive *a, bt_adaptive_stats *out) {
         BT_HIP(hipMemcpy(&s.active_tiles, a->d_n_active, 4, hipMemcpyDeviceToHost));
         s.min_count = *std::min_element(counts.begin(), counts.end());
         s.max_count = *std::max_element(counts.begin(), counts.end());
-        for (uint32_t t = 0; t < a->tiles(); ++t) {
-            const uint32_t tx = t % a->tiles_x, ty = t / a->tiles_x;
-            const uint32_t w = std::min<uint32_t>(BT_TILE, a->width - tx * BT_TILE), h = std::min<uint32_t>(BT_TILE, a->height - ty * BT_TILE);
-            s.pixel_samples += (uint64_t)w * h * counts[t];
-        }
+        s.pixel_samples = btplan::pixels_owned(a->width, a->height, 0, 1, counts.data());
         a->done = s.active_tiles == 0;
     }
     if (out) *out = s;

@@ -14,8 +14,7 @@
 #include <string>
 
 #include "../../include/bendy_hip.h"
-
-extern "C" int bt_set_error_internal(int code, const char *msg);      // bt_api.cpp
+#include "bt_internal.hpp"
 
 namespace {
 

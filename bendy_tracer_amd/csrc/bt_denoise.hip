@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "bt_internal.hpp"
+
 #pragma STDC FP_CONTRACT OFF
 
 namespace {

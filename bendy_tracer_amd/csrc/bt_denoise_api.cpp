@@ -6,21 +6,13 @@
 #include <string>
 
 #include "../../include/bendy_hip.h"
+#include "bt_internal.hpp"
 
 #pragma STDC FP_CONTRACT OFF
-
-extern "C" int bt_set_error_internal(int code, const char *msg);      // bt_api.cpp
-extern "C" hipError_t bt_launch_denoise(const float *color, float nc, const float *albedo, float na, const float *normal,
-                                        float nn, const float *depth, float nd, float *out, float *e0, float *e1,
-                                        float *guide, uint32_t width, uint32_t height, uint32_t levels, float sigma_color,
-                                        float sigma_normal, float sigma_depth, float eps_albedo, hipStream_t stream);
 
 namespace {
 
 constexpr uint32_t kMaxLevels = 10;
-
-int fail(int code, const std::string &msg) { return bt_set_error_internal(code, msg.c_str()); }
-int hip_fail(const char *what, hipError_t e) { return fail(BT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
 
 // Everything that can be checked without the device.  Returns 0 or BT_ERR_INVALID_ARG (with bt_last_error set).
 int validate(const bt_denoiser *d, const float *color, uint32_t color_samples, const float *albedo, uint32_t albedo_samples,

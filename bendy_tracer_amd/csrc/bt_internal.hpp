@@ -1,0 +1,50 @@
+// bt_internal.hpp -- everything that crosses translation units inside libbendy_hip.so and is not in include/bendy_hip.h.
+// Included by the file that defines each of these and by the files that call it: a declaration that does not match its
+// definition does not compile.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/bendy_hip.h"
+
+struct BtLaunch;
+struct BtSphereRow;
+
+extern "C" {
+// bt_kernels.hip
+hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned grid, size_t lds_bytes, hipStream_t stream);
+hipError_t bt_launch_unshard(const float *gathered, float *frame, uint32_t width, uint32_t height, uint32_t tiles_x,
+                             uint32_t tiles_y, uint32_t world, uint32_t tiles_per_rank, hipStream_t stream);
+void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows, uint32_t n_blocks, uint64_t *out);
+int bt_launch_reads_masks(const BtLaunch *P, int output);
+int bt_mask_cache_enabled(void);
+hipError_t bt_launch_block_masks(const BtLaunch *P, uint32_t n_blocks, uint64_t *masks, hipStream_t stream);
+hipError_t bt_launch_preview(const float *rgba, uint8_t *out, uint32_t n, uint32_t samples, int color_space, hipStream_t stream);
+// bt_adapt.hip
+hipError_t bt_launch_adapt_update(const float *rgba, const float *moment, uint32_t *count, uint32_t *active, float *error,
+                                  uint32_t *n_active, uint32_t width, uint32_t height, uint32_t T, const bt_adaptive_params *p,
+                                  hipStream_t stream);
+hipError_t bt_launch_adapt_resolve(const float *rgba, const uint32_t *count, float *out, uint32_t width, uint32_t height,
+                                   hipStream_t stream);
+// bt_denoise.hip
+hipError_t bt_launch_denoise(const float *color, float nc, const float *albedo, float na, const float *normal, float nn,
+                             const float *depth, float nd, float *out, float *e0, float *e1, float *guide, uint32_t width,
+                             uint32_t height, uint32_t levels, float sigma_color, float sigma_normal, float sigma_depth,
+                             float eps_albedo, hipStream_t stream);
+// bt_api.cpp
+int bt_set_error_internal(int code, const char *msg);      // sets bt_last_error / bt_last_error_code; returns `code`
+int bt_scene_lens_on_internal(const bt_scene *scene);
+// The render half of bt_render_adaptive_device (bt_adapt_api.cpp, which has validated everything).
+int bt_render_adaptive_pass_internal(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                                     float *rgba_device, uint32_t width, uint32_t height, uint64_t seed, void *stream,
+                                     const uint32_t *tile_active, float *moment);
+}
+
+static inline int fail(int code, const std::string &msg) { return bt_set_error_internal(code, msg.c_str()); }
+static inline int hip_fail(const char *what, hipError_t e) { return fail(BT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+#define BT_HIP(expr)                                        \
+    do {                                                    \
+        hipError_t _e = (expr);                             \
+        if (_e != hipSuccess) return hip_fail(#expr, _e);   \
+    } while (0)

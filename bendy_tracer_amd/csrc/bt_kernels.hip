@@ -42,6 +42,7 @@
 // r04e, r04f).
 #include "bt_device.hpp"
 #include "bt_cull.hpp"
+#include "bt_internal.hpp"
 
 #define BT_SUM_BATCH 8             // parked values a lane of the summing wave has in flight (16: no difference, profiles/r04k)
 

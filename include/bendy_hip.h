@@ -183,6 +183,16 @@ int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *con
                       uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint8_t *out,
                       uint32_t cap);
 
+/* For tests of the launch planner, on a machine without a GPU: what a render of these arguments on a device
+ * of `n_cu` compute units would launch.  pass_kind: 0 plain, 1 guided with `guides` = bit 0 albedo | bit 1 normal | bit 2
+ * depth present, 2 adaptive.  No device is touched: allocations of more than `alloc_limit` bytes fail (0 = none fails).
+ * Fills the launch-shape fields of `out` (slices, launches, packed, workgroups, scratch_bytes, parked_bytes, pixels,
+ * samples; the others 0) and returns 0, or the bt_status the render would fail with.  The first plan on a handle starts
+ * from an empty scratch; later ones from what the earlier ones left, as renders do (bt_scene_trim empties it). */
+int bt_debug_plan_launch(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                         uint32_t width, uint32_t height, uint32_t rank, uint32_t world, int32_t sharded, uint32_t n_cu,
+                         int32_t pass_kind, uint32_t guides, uint64_t alloc_limit, bt_stats *out);
+
 /* --- Tracer::render (tracer/mod.rs:179-202) ----------------------------------------
  * Adds `samples * n^2` radiance samples per pixel into the RGB channels of `rgba`
  * (row-major, 4 floats per pixel, alpha untouched: buffer.rs:159-178).  The caller
