@@ -5,8 +5,8 @@ into `libbendy_hip.so`) and `api.py` (host-side mirror of the reference's Rust A
 Importing the package loads the shared library; a missing library is an ImportError.
 """
 from .api import (Adaptive, AdaptiveParams, AdaptiveStats, BendyError, Buffer, ColorSpace, Comm, Config, DenoiseParams, Denoiser, Output, RenderConfig, Scene, Stats,
-                  Status, Subsample, Tracer, denoise, new_shard, shard_floats, tile_owner_map, unshard, write_png)
+                  Status, Subsample, Temporal, TemporalParams, Tracer, View, denoise, new_shard, reproject, shard_floats, tile_owner_map, unshard, write_png)
 
 __all__ = ["Adaptive", "AdaptiveParams", "AdaptiveStats", "BendyError", "Buffer", "ColorSpace", "Comm", "Config", "DenoiseParams", "Denoiser", "Output", "RenderConfig",
-           "Scene", "Stats", "Status", "Subsample", "Tracer", "denoise", "new_shard", "shard_floats", "tile_owner_map",
+           "Scene", "Stats", "Status", "Subsample", "Temporal", "TemporalParams", "Tracer", "View", "denoise", "new_shard", "reproject", "shard_floats", "tile_owner_map",
            "unshard", "write_png"]

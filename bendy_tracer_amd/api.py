@@ -145,6 +145,22 @@ class AdaptiveStats(C.Structure):  # include/bendy_hip.h `bt_adaptive_stats` (ex
                 ("pixel_samples", C.c_uint64), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class View(C.Structure):  # include/bendy_hip.h `bt_view` (extension): the camera as data
+    _fields_ = [("to_world", C.c_float * 12), ("yfov", C.c_float), ("xfov", C.c_float), ("clip_min", C.c_float),
+                ("clip_max", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32), ("subsample_n", C.c_uint32)]
+
+    def copy(self):
+        return View.from_buffer_copy(self)
+
+    def matrix(self):
+        """to_world as float32 [12]: columns x, y, z, then the translation."""
+        return np.array(self.to_world, dtype=np.float32)
+
+
+class _CTemporalParams(C.Structure):  # include/bendy_hip.h `bt_temporal_params` (extension)
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_min", C.c_float)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -163,6 +179,8 @@ EXPORTS = [
     "bt_render_guided_device", "bt_adaptive_params_default", "bt_adaptive_new", "bt_adaptive_free", "bt_adaptive_reset",
     "bt_render_adaptive_device", "bt_adaptive_poll", "bt_adaptive_counts", "bt_adaptive_errors", "bt_debug_adaptive_moments",
     "bt_adaptive_resolve_device",
+    "bt_scene_camera_view", "bt_scene_set_camera_pose", "bt_temporal_params_default", "bt_temporal_new", "bt_temporal_free",
+    "bt_temporal_reset", "bt_temporal_accumulate_device", "bt_debug_temporal_history", "bt_debug_reproject",
 ]
 
 
@@ -254,6 +272,18 @@ def _load():
     L.bt_adaptive_errors.argtypes = [vp, fp, C.c_uint32]
     L.bt_debug_adaptive_moments.argtypes = [vp, fp, C.c_uint32]
     L.bt_adaptive_resolve_device.argtypes = [vp, vp, vp, vp]
+    L.bt_scene_camera_view.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
+                                       C.POINTER(View)]
+    L.bt_scene_set_camera_pose.argtypes = [vp, C.c_uint64, fp]
+    L.bt_temporal_params_default.argtypes = [C.POINTER(_CTemporalParams)]
+    L.bt_temporal_new.restype = vp
+    L.bt_temporal_new.argtypes = [C.c_uint32, C.c_uint32]
+    L.bt_temporal_free.argtypes = [vp]
+    L.bt_temporal_reset.argtypes = [vp]
+    L.bt_temporal_accumulate_device.argtypes = [vp, C.POINTER(View), vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp,
+                                                C.POINTER(_CTemporalParams), vp]
+    L.bt_debug_temporal_history.argtypes = [vp, fp, C.c_uint32]
+    L.bt_debug_reproject.argtypes = [C.POINTER(View), C.POINTER(View), C.c_float, C.c_float, C.c_float, fp]
     return L
 
 
@@ -337,6 +367,22 @@ class Scene:
         """bt_debug_set_object (tests): move an object / resize a sphere in place on this handle."""
         t = None if translation is None else (C.c_float * 3)(*[float(v) for v in translation])
         _check(lib.bt_debug_set_object(self._h, object_ref, t, float(radius)))
+
+    def camera_view(self, camera, config: "Config", render: "RenderConfig", width, height) -> View:
+        """EXTENSION, not in the reference (bt_scene_camera_view): the camera as data -- what a render with
+        these arguments puts into its launch.  Touches no device."""
+        c, r = _c_configs(config, render, 0)
+        v = View()
+        _check(lib.bt_scene_camera_view(self._h, camera, C.byref(c), C.byref(r), width, height, C.byref(v)))
+        return v
+
+    def set_camera_pose(self, camera, to_world):
+        """EXTENSION, not in the reference (bt_scene_set_camera_pose): replaces the camera's transform_world in place on this
+        handle; 12 floats, columns x, y, z, then the translation.  The JSON that `save` / `to_json` write is not updated."""
+        m = [float(v) for v in np.asarray(to_world, dtype=np.float32).reshape(-1)]
+        if len(m) != 12:
+            raise BendyError(-1, f"to_world needs 12 floats, not {len(m)}")
+        _check(lib.bt_scene_set_camera_pose(self._h, camera, (C.c_float * 12)(*m)))
 
     def set_lens(self, centre, rs, step, radius, max_steps=4096):
         """EXTENSION, not in the reference (include/bendy_hip.h `bt_lens`): bend rays around a point mass."""
@@ -829,6 +875,103 @@ class Adaptive:
                                               torch.cuda.current_stream().cuda_stream))
         out.samples = 1
         return out
+
+
+def _temporal_defaults():
+    p = _CTemporalParams()
+    lib.bt_temporal_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class TemporalParams:
+    """`bt_temporal_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_temporal_params_default's value."""
+    alpha_min: Optional[float] = None
+    max_history: Optional[float] = None
+    depth_tolerance: Optional[float] = None
+    normal_min: Optional[float] = None
+
+    def __post_init__(self):
+        d = _temporal_defaults()
+        for k, _ in _CTemporalParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+
+    def _c(self):
+        return _CTemporalParams(float(self.alpha_min), float(self.max_history), float(self.depth_tolerance), float(self.normal_min))
+
+
+class Temporal:
+    """`bt_temporal` (include/bendy_hip.h): EXTENSION, not in the reference -- temporal accumulation with reprojection for one
+    frame size.  The handle owns the previous frame's accumulated colour and guides (64 B per pixel) and the
+    previous view.  Keywords = TemporalParams fields."""
+
+    def __init__(self, width, height, **params):
+        self.params = TemporalParams(**params)
+        self.width, self.height = int(width), int(height)
+        h = lib.bt_temporal_new(self.width, self.height)
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_temporal_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        """Forgets the history and the previous view."""
+        _check(lib.bt_temporal_reset(self._h))
+
+    def accumulate(self, view: View, color: Buffer, normal: Optional[Buffer] = None, depth: Optional[Buffer] = None, *,
+                   out: Optional[Buffer] = None, **params) -> Buffer:
+        """Blends this frame's running sums (`color`, `normal`, `depth`, each divided by its own `.samples`; what
+        `Tracer.render_guided` wrote into cleared buffers under `view`) into the history reprojected from the previous call's
+        view.  `depth` is required, `normal` may be None.  Returns `out` (a new Buffer by default) holding the MEAN with
+        samples = 1 and the colour buffer's color_space, so `.preview()` and `denoise(...)` work unchanged.  Keywords
+        override the handle's TemporalParams for this call."""
+        p = TemporalParams(**{**{k: getattr(self.params, k) for k, _ in _CTemporalParams._fields_}, **params})
+        if depth is None:
+            raise BendyError(-1, "accumulate needs the frame's depth buffer")
+        bufs = [b for b in (normal, depth) if b is not None]
+        for b in [color] + bufs + ([out] if out is not None else []):
+            if b.device == "cpu":
+                raise BendyError(-1, "accumulate needs device-resident buffers (there is no host-buffer variant)")
+            if (b.width, b.height) != (self.width, self.height):
+                raise BendyError(-1, f"buffer of {b.width}x{b.height} on a temporal handle of {self.width}x{self.height}")
+        if out is not None and any(out is b or out.data is b.data for b in [color] + bufs):
+            raise BendyError(-1, "out must not be one of the inputs: the inputs are running sums, out is a mean")
+        if out is None:
+            out = Buffer(color.width, color.height, color.color_space, device=color.device)
+        out.color_space = color.color_space
+        cp = p._c()
+        import torch
+        _check(lib.bt_temporal_accumulate_device(self._h, C.byref(view), color.data.data_ptr(), color.samples,
+                                                 normal.data.data_ptr() if normal is not None else None,
+                                                 normal.samples if normal is not None else 0, depth.data.data_ptr(),
+                                                 depth.samples, out.data.data_ptr(), C.byref(cp),
+                                                 torch.cuda.current_stream().cuda_stream))
+        out.samples = 1
+        return out
+
+    def history(self):
+        """bt_debug_temporal_history (tests; synchronises): float32 [height, width, 4], rgb = the accumulated mean, a = the
+        history length in samples per pixel; zeros while there is no history."""
+        n = _check(lib.bt_debug_temporal_history(self._h, None, 0))
+        out = np.zeros(n, dtype=np.float32)
+        _check(lib.bt_debug_temporal_history(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return out.reshape(self.height, self.width, 4)
+
+
+def reproject(cur: View, prev: View, x, y, z):
+    """bt_debug_reproject (tests; host code, no device): where pixel (x, y) of `cur` at normalised depth z (z >= 1: at
+    infinity) lies in `prev`: (x_f, y_f, z')."""
+    out = (C.c_float * 3)()
+    _check(lib.bt_debug_reproject(C.byref(cur), C.byref(prev), x, y, z, out))
+    return (out[0], out[1], out[2])
 
 
 _default_denoiser = None

@@ -16,11 +16,16 @@
 // --adaptive THRESHOLD [--adaptive-min N] [--adaptive-map PATH] (extension too; bt_adaptive): every call is one adaptive pass of
 // --samples-per-call samples into the 16x16 tiles whose error estimate is still above THRESHOLD, --samples is the cap per tile,
 // the loop ends when no tile is active; the screenshot (and what --denoise filters) is the resolved mean.
+// --temporal [--frames N] [--camera-step X,Y,Z] (extension too; bt_temporal): N displayed frames; each clears the colour and guide
+// frames, renders --samples x subsample^2 rays per pixel through the guided pass and accumulates them into the history
+// reprojected from the frame before; the camera moves by the world-space step X,Y,Z before every frame after the first.  The
+// screenshot is the last frame's accumulated mean (with --denoise: filtered with that frame's own guides).
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -92,6 +97,10 @@ struct Args {
     float adaptive_threshold = 0.0f;
     long adaptive_min = -1;                               // -1: bt_adaptive_params_default's
     std::string adaptive_map;
+    bool temporal = false;
+    long frames = -1;                                     // -1: not given (1 with --temporal)
+    bool has_camera_step = false;
+    float camera_step[3] = {0.0f, 0.0f, 0.0f};
 };
 
 void usage() {
@@ -106,7 +115,10 @@ void usage() {
                  "                             --denoise, --shard or --lens)\n"
                  "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-map PATH]   (extension: adaptive sampling; --samples is\n"
                  "                             the cap, --samples-per-call the pass; --output full only, not with --lens, --shard\n"
-                 "                             or --denoise-inline)\n");
+                 "                             or --denoise-inline)\n"
+                 "       [--temporal] [--frames N] [--camera-step X,Y,Z]   (extension: temporal accumulation with reprojection; N frames\n"
+                 "                             of --samples each, the camera moved by X,Y,Z before each frame after the first;\n"
+                 "                             --output full only, not with --lens, --shard, --adaptive or --denoise-inline)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -164,6 +176,21 @@ Args parse(int argc, char **argv) {
         }
         else if (k == "--adaptive-min") a.adaptive_min = (long)std::strtoul(val().c_str(), nullptr, 10);
         else if (k == "--adaptive-map") a.adaptive_map = val();
+        else if (k == "--temporal") a.temporal = true;
+        else if (k == "--frames") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.frames = std::strtol(spec.c_str(), &end, 10);
+            if (spec.empty() || *end != 0 || a.frames < 1 || a.frames > 1000000) die("--frames expects a count >= 1");
+        }
+        else if (k == "--camera-step") {
+            const std::string spec = val();
+            char tail = 0;
+            if (std::sscanf(spec.c_str(), "%f,%f,%f%c", &a.camera_step[0], &a.camera_step[1], &a.camera_step[2], &tail) != 3 ||
+                !(std::fabs(a.camera_step[0]) < 3.0e38f) || !(std::fabs(a.camera_step[1]) < 3.0e38f) || !(std::fabs(a.camera_step[2]) < 3.0e38f))
+                die("--camera-step expects X,Y,Z (finite)");
+            a.has_camera_step = true;
+        }
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -182,6 +209,14 @@ Args parse(int argc, char **argv) {
     if (a.adaptive && a.shard_world > 1) die("--adaptive does not apply to a --shard run");
     if (a.adaptive && a.denoise_inline) die("--adaptive has no guided variant: use --denoise, not --denoise-inline");
     if (a.adaptive && a.adaptive_min > (long)a.samples) die("--adaptive-min must not exceed --samples (the cap)");
+    if (!a.temporal && (a.frames >= 0 || a.has_camera_step)) die("--frames and --camera-step need --temporal");
+    if (a.temporal && a.output != "full") die("--temporal needs --output full");
+    if (a.temporal && a.has_lens) die("--temporal has no inverse map for --lens");
+    if (a.temporal && a.shard_world > 1) die("--temporal does not apply to a --shard run");
+    if (a.temporal && a.adaptive) die("--temporal does not take the frames of --adaptive, whose tiles hold different counts");
+    if (a.temporal && a.denoise_inline) die("--temporal renders its own guides: use --denoise, not --denoise-inline");
+    if (a.temporal && a.samples == 0) die("--temporal needs --samples >= 1 per frame");
+    if (a.temporal && a.frames < 0) a.frames = 1;
     return a;
 }
 
@@ -248,7 +283,7 @@ int main(int argc, char **argv) {
 
     // --denoise-inline (extension): the guides' frames and the denoised mean; every call below fills all four in one pass
     float *d_guides[4] = {nullptr, nullptr, nullptr, nullptr};          // albedo, normal, depth, denoised mean
-    if (args.denoise_inline)
+    if (args.denoise_inline || args.temporal)
         for (int g = 0; g < 4; ++g) {
             hip_check(hipMalloc((void **)&d_guides[g], n_px * 16), "hipMalloc");
             hip_check(hipMemcpy(d_guides[g], init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
@@ -298,7 +333,58 @@ int main(int argc, char **argv) {
         check(bt_adaptive_resolve_device(adaptive, d_frame, d_mean, nullptr), "bt_adaptive_resolve_device");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     }
-    while (!args.adaptive && buffer_samples < args.samples) {
+    // --temporal (extension): one guided render into cleared frames and one accumulate per displayed frame
+    bt_temporal *temporal = nullptr;
+    double history_mean = 0.0, history_min = 0.0;
+    if (args.temporal) {
+        temporal = bt_temporal_new(args.width, args.height);
+        if (!temporal) die(bt_last_error());
+        hip_check(hipMalloc((void **)&d_mean, n_px * 16), "hipMalloc");
+        rc.samples = args.samples;
+        bt_view view;
+        check(bt_scene_camera_view(scene, camera, &cfg, &rc, args.width, args.height, &view), "bt_scene_camera_view");
+        for (long f = 0; f < args.frames; ++f) {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (f > 0) {
+                for (int k = 0; k < 3; ++k) view.to_world[9 + k] += args.camera_step[k];
+                check(bt_scene_set_camera_pose(scene, camera, view.to_world), "bt_scene_set_camera_pose");
+            }
+            hip_check(hipMemcpy(d_frame, init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
+            for (int g = 0; g < 3; ++g) hip_check(hipMemcpy(d_guides[g], init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
+            rc.sample_base = (uint32_t)f * args.samples;   // fresh samples every frame
+            check(bt_render_guided_device(scene, camera, &cfg, &rc, d_frame, d_guides[0], d_guides[1], d_guides[2], args.width,
+                                          args.height, args.seed, nullptr),
+                  "bt_render_guided_device");
+            check(bt_temporal_accumulate_device(temporal, &view, d_frame, args.samples * nn, d_guides[1], args.samples * nn, d_guides[2],
+                                                args.samples * nn, d_mean, nullptr, nullptr),
+                  "bt_temporal_accumulate_device");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            const double delta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            sum_delta += delta;
+            buffer_samples += args.samples * nn;
+            if (!args.stats_json.empty()) {
+                bt_stats cs{};
+                bt_scene_last_stats(scene, &cs);
+                char row[256];
+                std::snprintf(row, sizeof row, "%s{\"kernel_ms\": %.5f, \"segments\": %llu, \"samples\": %llu, \"pixels\": %llu, \"slices\": %u, \"packed\": %u}",
+                              per_call.empty() ? "" : ", ", cs.kernel_ms, (unsigned long long)cs.segments,
+                              (unsigned long long)cs.samples, (unsigned long long)cs.pixels, cs.slices, cs.packed);
+                per_call += row;
+            }
+            if (!args.quiet)
+                std::fprintf(stderr, "bendy tracer; temporal frame %ld/%ld; samples per frame: %u; delta t: %s\n", f + 1, args.frames,
+                             args.samples * nn, fmt_duration(delta).c_str());
+        }
+        std::vector<float> hist(n_px * 4);
+        check(bt_debug_temporal_history(temporal, hist.data(), (uint32_t)(n_px * 4)), "bt_debug_temporal_history");
+        history_min = hist[3];
+        for (size_t i = 0; i < n_px; ++i) {
+            history_mean += hist[4 * i + 3];
+            history_min = std::min(history_min, (double)hist[4 * i + 3]);
+        }
+        history_mean /= (double)n_px;
+    }
+    while (!args.adaptive && !args.temporal && buffer_samples < args.samples) {
         rc.samples = std::min(args.samples_per_call, std::max(1u, (args.samples - buffer_samples) / nn));
         rc.sample_base = (buffer_samples + nn - 1) / nn;
         const auto t0 = std::chrono::steady_clock::now();
@@ -329,6 +415,8 @@ int main(int argc, char **argv) {
     const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     bt_stats stats{};
     bt_scene_last_stats(scene, &stats);
+    if (args.temporal)
+        std::fprintf(stderr, "temporal: %ld frames, history length mean %.2f, min %.2f samples per pixel\n", args.frames, history_mean, history_min);
     std::fprintf(stderr, "bendy tracer; samples: %u/%u; avg t per sample: %s; total t: %s\n", buffer_samples, args.samples,
                  fmt_duration(buffer_samples ? sum_delta / buffer_samples : 0.0).c_str(), fmt_duration(total).c_str());
     if (args.adaptive)
@@ -346,6 +434,9 @@ int main(int argc, char **argv) {
         if (args.adaptive)
             std::snprintf(ad, sizeof ad, ", \"adaptive\": {\"active_tiles\": %u, \"tiles\": %u, \"min_count\": %u, \"max_count\": %u, \"pixel_samples\": %llu, \"passes\": %u}",
                           astats.active_tiles, astats.tiles, astats.min_count, astats.max_count, (unsigned long long)astats.pixel_samples, astats.passes);
+        if (args.temporal)
+            std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
+                          history_mean, history_min);
         std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s}\n", args.width,
                      args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad);
         std::fclose(f);
@@ -371,6 +462,10 @@ int main(int argc, char **argv) {
     // --denoise (extension): the guides of the same frame into fresh buffers, then the screenshot shows the denoised mean
     float *d_shown = d_frame;
     unsigned shown_samples = buffer_samples ? buffer_samples : 1;
+    if (args.temporal) {                                    // everything below sees the accumulated mean
+        d_shown = d_mean;
+        shown_samples = 1;
+    }
     if (args.adaptive) {                                    // everything below sees the resolved mean
         d_shown = d_mean;
         shown_samples = 1;
@@ -400,7 +495,18 @@ int main(int argc, char **argv) {
         shown_samples = 1;                                  // the denoised buffer holds a mean
         std::fprintf(stderr, "denoised with in-pass guides of %u samples\n", buffer_samples);
     }
-    if (args.denoise && !args.no_screenshot) {
+    if (args.denoise && args.temporal && !args.no_screenshot) {      // the last frame's own guides, rendered with its colour
+        const uint32_t gs = args.samples * nn;
+        bt_denoiser *dn = bt_denoiser_new();
+        check(bt_denoise_device(dn, d_shown, shown_samples, d_guides[0], gs, d_guides[1], gs, d_guides[2], gs, d_guides[3],
+                                args.width, args.height, nullptr, nullptr),
+              "bt_denoise_device");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bt_denoiser_free(dn);
+        d_shown = d_guides[3];
+        std::fprintf(stderr, "denoised with the last frame's guides of %u samples\n", gs);
+    }
+    if (args.denoise && !args.temporal && !args.no_screenshot) {
         for (int g = 0; g < 4; ++g) {
             hip_check(hipMalloc((void **)&d_guides[g], n_px * 16), "hipMalloc");
             hip_check(hipMemcpy(d_guides[g], init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
@@ -445,6 +551,7 @@ int main(int argc, char **argv) {
     (void)hipFree(d_rgba8);
     if (d_mean) (void)hipFree(d_mean);
     bt_adaptive_free(adaptive);
+    bt_temporal_free(temporal);
     for (float *g : d_guides)
         if (g) (void)hipFree(g);
     bt_scene_free(scene);

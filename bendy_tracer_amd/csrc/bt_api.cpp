@@ -664,6 +664,41 @@ int bt_debug_set_object(bt_scene *scene, uint64_t object_ref, const float *trans
     return 0;
 }
 
+// EXTENSION (bt_view): the camera fields fill_launch puts into BtLaunch, without the tables or a device
+int bt_scene_camera_view(const bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                         uint32_t width, uint32_t height, bt_view *out) {
+    if (!scene || !config || !render || !out) return fail(BT_ERR_INVALID_ARG, "null argument");
+    if (width == 0 || height == 0) return fail(BT_ERR_INVALID_ARG, "zero-sized buffer");
+    const int i = scene->scene.object_index(camera_ref);
+    if (i < 0) return fail(BT_ERR_INVALID_REF, "invalid object ref " + std::to_string(camera_ref));
+    const bt::Object &cam = scene->scene.objects[i];
+    if (cam.kind != bt::OBJ_CAMERA) return fail(BT_ERR_NOT_CAMERA, "expected a camera object");
+    const BtV3 col[4] = {cam.world.cx, cam.world.cy, cam.world.cz, cam.world.t};
+    for (int c = 0; c < 4; ++c) { out->to_world[3 * c] = col[c].x; out->to_world[3 * c + 1] = col[c].y; out->to_world[3 * c + 2] = col[c].z; }
+    out->yfov = 2.0f * atan2f(cam.sensor_size, 2.0f * cam.focal_length);  // mod.rs:248
+    out->xfov = out->yfov * cam.aspect_ratio;                             // mod.rs:249
+    out->clip_min = config->clip_min;
+    out->clip_max = config->clip_max;
+    out->width = width;
+    out->height = height;
+    out->subsample_n = render->subsample_n;
+    return 0;
+}
+
+int bt_scene_set_camera_pose(bt_scene *scene, uint64_t camera_ref, const float *to_world) {
+    if (!scene || !to_world) return fail(BT_ERR_INVALID_ARG, "null argument");
+    const int i = scene->scene.object_index(camera_ref);
+    if (i < 0) return fail(BT_ERR_INVALID_REF, "invalid object ref " + std::to_string(camera_ref));
+    bt::Object &o = scene->scene.objects[i];
+    if (o.kind != bt::OBJ_CAMERA) return fail(BT_ERR_NOT_CAMERA, "expected a camera object");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(to_world[k])) return fail(BT_ERR_INVALID_ARG, "non-finite entry in to_world");
+    BtV3 *col[4] = {&o.world.cx, &o.world.cy, &o.world.cz, &o.world.t};
+    for (int c = 0; c < 4; ++c) { col[c]->x = to_world[3 * c]; col[c]->y = to_world[3 * c + 1]; col[c]->z = to_world[3 * c + 2]; }
+    scene->flat_valid = false;                            // as bt_debug_set_object: flattened and uploaded again by the next render
+    return 0;
+}
+
 // the launch the bt_debug_* mask entry points describe: fill_launch + shard and block shape; returns the number of blocks
 static int debug_mask_launch(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
                              uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, BtLaunch &P) {

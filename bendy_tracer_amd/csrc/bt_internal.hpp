@@ -7,9 +7,20 @@
 #include <string>
 
 #include "../../include/bendy_hip.h"
+#include "bt_view.hpp"
 
 struct BtLaunch;
 struct BtSphereRow;
+
+// One launch of the temporal kernel (bt_temporal.hip), passed by value.  The planes are width * height float4 each.
+struct BtTemporalLaunch {
+    btview::View cur, prev;                  // prev: read by the reprojecting build only
+    const float4 *color, *normal, *depth;    // this frame's running sums; normal may be null
+    float nc, nn, nd;                        // their sample counts
+    const float4 *hist_in, *guide_in;        // the previous frame's history (rgb = mean, a = length) and guides (n.xyz, z)
+    float4 *hist_out, *guide_out, *out;
+    float alpha_min, max_history, depth_tolerance, normal_min;
+};
 
 extern "C" {
 // bt_kernels.hip
@@ -32,6 +43,8 @@ hipError_t bt_launch_denoise(const float *color, float nc, const float *albedo, 
                              const float *depth, float nd, float *out, float *e0, float *e1, float *guide, uint32_t width,
                              uint32_t height, uint32_t levels, float sigma_color, float sigma_normal, float sigma_depth,
                              float eps_albedo, hipStream_t stream);
+// bt_temporal.hip: mode 0 = no history, 1 = the previous view again, 2 = reproject
+hipError_t bt_launch_temporal(const BtTemporalLaunch *P, int mode, hipStream_t stream);
 // bt_api.cpp
 int bt_set_error_internal(int code, const char *msg);      // sets bt_last_error / bt_last_error_code; returns `code`
 int bt_scene_lens_on_internal(const bt_scene *scene);

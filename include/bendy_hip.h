@@ -370,6 +370,76 @@ int bt_debug_adaptive_moments(bt_adaptive *a, float *host, uint32_t n);
  * with samples = 1 or handed to bt_denoise_device with color_samples = 1.  `out` must not be `rgba`. */
 int bt_adaptive_resolve_device(bt_adaptive *a, const float *rgba_device, float *out_device, void *stream);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: temporal accumulation with reprojection --------------------
+ * bendy-tracer v1 throws every sample of a frame buffer away when the camera moves (Buffer::clear, main.rs:325).  This
+ * stage is off unless called, makes no parity claim and changes no render.  It keeps the previous frame's accumulated
+ * colour and guides, finds where each pixel of the new frame was in the old one and blends (the temporal stage of SVGF,
+ * Schied et al. 2017, without its variance history).  The world is assumed static: only the camera moves.
+ *
+ * bt_view is the camera as data: what a render with the same arguments puts into its launch. */
+typedef struct {
+    float to_world[12];        /* the camera's transform_world: columns x, y, z, then the translation */
+    float yfov, xfov;          /* 2 atan2(sensor, 2 focal) and yfov * aspect (mod.rs:248-249) */
+    float clip_min, clip_max;
+    uint32_t width, height, subsample_n;   /* subsample_n as in bt_render_config: 0 / 1 = None */
+} bt_view;
+/* Touches no device.  BT_ERR_INVALID_REF / BT_ERR_NOT_CAMERA as renders do; NULL arguments or a zero-sized frame ->
+ * BT_ERR_INVALID_ARG. */
+int bt_scene_camera_view(const bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
+                         uint32_t width, uint32_t height, bt_view *out);
+/* Replaces the camera's transform_world IN PLACE (12 floats, laid out as bt_view.to_world); the next render flattens and
+ * uploads the tables again, as after bt_debug_set_object.  BT_ERR_NOT_CAMERA for another kind of object,
+ * BT_ERR_INVALID_ARG for a non-finite entry.  The JSON that bt_scene_save / bt_scene_to_json write is not updated. */
+int bt_scene_set_camera_pose(bt_scene *scene, uint64_t camera_ref, const float *to_world);
+
+typedef struct {
+    float alpha_min;           /* [0, 1]: floor of the blend weight of the new frame */
+    float max_history;         /* >= 1, finite: the history length (in samples per pixel) is clamped to this */
+    float depth_tolerance;     /* >= 0: a tap passes if |z' - z_q| <= depth_tolerance * z' */
+    float normal_min;          /* [-1, 1]: a tap passes if n_p . n_q >= normal_min */
+} bt_temporal_params;
+typedef struct bt_temporal bt_temporal;   /* owns two history and two guide planes (64 B per pixel) and the previous view;
+                                           * one frame size, one stream at a time */
+void bt_temporal_params_default(bt_temporal_params *out);
+/* No device work happens here: the planes are allocated by the first accumulate, on the device current then.  NULL for a
+ * zero-sized frame. */
+bt_temporal *bt_temporal_new(uint32_t width, uint32_t height);
+void bt_temporal_free(bt_temporal *t);
+/* Forgets the history and the previous view: the next accumulate writes the frame's own mean. */
+int bt_temporal_reset(bt_temporal *t);
+/* One kernel on `stream`; returns without synchronising.  The inputs are RGBA32F running sums of THIS frame alone (what
+ * bt_render_guided_device wrote into cleared buffers), each with its own sample count; `normal` may be NULL (the normal
+ * test then always passes), `depth` is required.  `out` receives the MEAN (preview it with samples = 1, or hand it to
+ * bt_denoise_device with color_samples = 1); out.a = the colour buffer's alpha.  Per pixel (x, y), in float32:
+ *     c = C.rgb / n_c;  n = the normalised mean normal (0 if shorter than 1e-6);  z = D.r / n_d;  far = z >= 1
+ *     first call since _new / _reset: out.rgb = c, history length = n_c
+ *     `view` bitwise equal to the previous call's: the pixel's own history is taken, weight W = 1, untested (the same pose
+ *     and a static world: a silhouette pixel whose samples hit in one frame and all miss in the next keeps its history)
+ *     else the pixel's point -- the ray through the centre of its sample footprint at distance clip_min + z (clip_max -
+ *     clip_min), or the ray's direction if far -- is projected into the previous view: (x_f, y_f) there, z' its
+ *     normalised distance from the previous camera; the four bilinear taps of the previous history around (x_f, y_f): one is dropped if it lies outside the frame, if
+ *     its depth z_q fails (far: z_q >= 1; else z_q < 1 and |z' - z_q| <= depth_tolerance z') or its normal n_q fails
+ *     (both zero: pass; one zero: fail; else n . n_q >= normal_min); W = the surviving weight
+ *     W < 1e-3: as on the first call; else m, h = the weighted history colour and length, N = min(h + n_c, max_history),
+ *     a = min(1, max(n_c / N, alpha_min)), out.rgb = m + (c - m) a, history length = N.
+ * A camera that does not move accumulates the running mean.  Depth-of-field origin jitter is ignored by the projection.
+ * Checked before the device is touched, in this order, all BT_ERR_INVALID_ARG: NULL handle / view / colour / depth /
+ * out; a sample count of 0 for a buffer that is given; view.width / height other than the handle's; a non-finite view
+ * entry, a field of view <= 0, clip_max <= clip_min or a singular to_world (|det| < 1e-12); a parameter outside its
+ * range; `out` equal to an input.  A valid call without a device returns BT_ERR_DEVICE.  params == NULL: the defaults.
+ * Not provided: a variance history, moving objects, sharded frames, host buffers, the lens extension and adaptively
+ * sampled frames (whose tiles hold different counts). */
+int bt_temporal_accumulate_device(bt_temporal *t, const bt_view *view, const float *color, uint32_t color_samples,
+                                  const float *normal, uint32_t normal_samples, const float *depth, uint32_t depth_samples,
+                                  float *out, const bt_temporal_params *params, void *stream);
+/* For tests: the current history plane, RGBA (rgb = accumulated mean, a = history length), row-major; zeros while there is
+ * none.  n == 0 returns the number of floats, else up to n are copied to `host` (synchronises) and the number copied is
+ * returned. */
+int bt_debug_temporal_history(bt_temporal *t, float *host, uint32_t n);
+/* For tests, on the host, by the code the kernel runs (bt_view.hpp): where pixel (x, y) of `cur` at normalised depth z
+ * (z >= 1: at infinity) lies in `prev`: out = (x_f, y_f, z').  BT_ERR_INVALID_ARG for a view the accumulate would refuse. */
+int bt_debug_reproject(const bt_view *cur, const bt_view *prev, float x, float y, float z, float *out);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);
