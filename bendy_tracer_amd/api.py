@@ -45,6 +45,12 @@ class ColorSpace(enum.IntEnum):  # tracer/buffer.rs:11-17
     SRgb = 3
 
 
+class Tonemap(enum.IntEnum):  # include/bendy_hip.h `bt_tonemap` (extension)
+    Clip = 0
+    Reinhard = 1
+    Aces = 2
+
+
 class Status(enum.IntEnum):  # tracer/mod.rs:159-163
     Done = 0
     InProgress = 1
@@ -161,6 +167,11 @@ class _CTemporalParams(C.Structure):  # include/bendy_hip.h `bt_temporal_params`
     _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_min", C.c_float)]
 
 
+class _CDisplayParams(C.Structure):  # include/bendy_hip.h `bt_display_params` (extension)
+    _fields_ = [("key", C.c_double), ("tonemap", C.c_int32), ("auto_exposure", C.c_int32), ("ev", C.c_float), ("p_low", C.c_float),
+                ("p_high", C.c_float), ("adapt", C.c_float), ("ev_min", C.c_float), ("ev_max", C.c_float), ("white", C.c_float)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -181,6 +192,8 @@ EXPORTS = [
     "bt_adaptive_resolve_device",
     "bt_scene_camera_view", "bt_scene_set_camera_pose", "bt_temporal_params_default", "bt_temporal_new", "bt_temporal_free",
     "bt_temporal_reset", "bt_temporal_accumulate_device", "bt_debug_temporal_history", "bt_debug_reproject",
+    "bt_display_params_default", "bt_display_new", "bt_display_free", "bt_display_reset", "bt_display_device",
+    "bt_display_exposure", "bt_debug_display_histogram", "bt_write_pfm",
 ]
 
 
@@ -284,6 +297,15 @@ def _load():
                                                 C.POINTER(_CTemporalParams), vp]
     L.bt_debug_temporal_history.argtypes = [vp, fp, C.c_uint32]
     L.bt_debug_reproject.argtypes = [C.POINTER(View), C.POINTER(View), C.c_float, C.c_float, C.c_float, fp]
+    L.bt_display_params_default.argtypes = [C.POINTER(_CDisplayParams)]
+    L.bt_display_new.restype = vp
+    L.bt_display_new.argtypes = []
+    L.bt_display_free.argtypes = [vp]
+    L.bt_display_reset.argtypes = [vp]
+    L.bt_display_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(_CDisplayParams), vp]
+    L.bt_display_exposure.argtypes = [vp, fp, fp]
+    L.bt_debug_display_histogram.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32]
+    L.bt_write_pfm.argtypes = [C.c_char_p, fp, C.c_uint32, C.c_uint32, C.c_uint32]
     return L
 
 
@@ -974,6 +996,91 @@ def reproject(cur: View, prev: View, x, y, z):
     return (out[0], out[1], out[2])
 
 
+def _display_defaults():
+    p = _CDisplayParams()
+    lib.bt_display_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class DisplayParams:
+    """`bt_display_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_display_params_default's value; `tonemap` is a Tonemap, its name ("aces") or its number."""
+    tonemap: Optional[int] = None
+    auto_exposure: Optional[int] = None
+    ev: Optional[float] = None
+    key: Optional[float] = None
+    p_low: Optional[float] = None
+    p_high: Optional[float] = None
+    adapt: Optional[float] = None
+    ev_min: Optional[float] = None
+    ev_max: Optional[float] = None
+    white: Optional[float] = None
+
+    def __post_init__(self):
+        d = _display_defaults()
+        for k, _ in _CDisplayParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+        if isinstance(self.tonemap, str):
+            self.tonemap = {t.name.lower(): t for t in Tonemap}[self.tonemap.lower()]
+
+    def _c(self):
+        return _CDisplayParams(float(self.key), int(self.tonemap), int(self.auto_exposure),
+                               *(float(getattr(self, k)) for k, _ in _CDisplayParams._fields_[3:]))
+
+
+class Display:
+    """`bt_display` (include/bendy_hip.h): EXTENSION, not in the reference -- the display stage: metered auto-exposure, adapted
+    from call to call, and a tone operator between the mean and the colour space.  The handle owns the
+    luminance counters and the adaptation state on the device.  Keywords = DisplayParams fields."""
+
+    def __init__(self, **params):
+        self.params = DisplayParams(**params)
+        h = lib.bt_display_new()
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_display_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self):
+        """Forgets the adaptation state and the last call."""
+        _check(lib.bt_display_reset(self._h))
+
+    def present(self, buffer: Buffer, **params):
+        """The frame of `buffer` (running sums of `.samples` samples, or a mean with samples = 1) metered, exposed and mapped
+        through the tone operator and the buffer's colour space -> uint8 [H, W, 4] on the host.  Keywords override the
+        handle's DisplayParams for this call."""
+        p = DisplayParams(**{**{k: getattr(self.params, k) for k, _ in _CDisplayParams._fields_}, **params})
+        if buffer.device == "cpu":
+            raise BendyError(-1, "present needs a device-resident buffer (there is no host-buffer variant)")
+        import torch
+        out = torch.empty((buffer.height, buffer.width, 4), dtype=torch.uint8, device=buffer.data.device)
+        cp = p._c()
+        _check(lib.bt_display_device(self._h, buffer.data.data_ptr(), max(buffer.samples, 1), out.data_ptr(), buffer.width,
+                                     buffer.height, int(buffer.color_space), C.byref(cp),
+                                     torch.cuda.current_stream().cuda_stream))
+        return out.cpu().numpy()
+
+    def exposure(self):
+        """(ev, mult) the last `present` showed its frame with (synchronises)."""
+        ev, mult = C.c_float(), C.c_float()
+        _check(lib.bt_display_exposure(self._h, C.byref(ev), C.byref(mult)))
+        return ev.value, mult.value
+
+    def histogram(self):
+        """bt_debug_display_histogram (tests; synchronises): (uint32 [256] luminance bins, under, over) of the last metered call."""
+        out = np.zeros(258, dtype=np.uint32)
+        _check(lib.bt_debug_display_histogram(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), 258))
+        return out[:256].copy(), int(out[256]), int(out[257])
+
+
 _default_denoiser = None
 
 
@@ -990,6 +1097,12 @@ def write_png(path, rgba8):
     """buffer.preview().save(path) (main.rs:275-298)."""
     a = np.ascontiguousarray(rgba8, dtype=np.uint8)
     _check(lib.bt_write_png(os.fspath(path).encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]))
+
+
+def write_pfm(path, rgba, samples=1):
+    """EXTENSION, not in the reference: the linear mean rgb * (1 / samples) of a float32 [H, W, 4] frame as a Portable Float Map."""
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    _check(lib.bt_write_pfm(os.fspath(path).encode(), a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[1], a.shape[0], int(samples)))
 
 
 def shard_floats(width, height, world):

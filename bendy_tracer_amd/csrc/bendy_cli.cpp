@@ -20,6 +20,10 @@
 // frames, renders --samples x subsample^2 rays per pixel through the guided pass and accumulates them into the history
 // reprojected from the frame before; the camera moves by the world-space step X,Y,Z before every frame after the first.  The
 // screenshot is the last frame's accumulated mean (with --denoise: filtered with that frame's own guides).
+// --tonemap clip|reinhard|aces, --exposure auto|EV [--exposure-key K] [--exposure-adapt A] [--white W] (extension too; bt_display):
+// with any of them the screenshot comes from bt_display_device instead of bt_preview_device, applied to whatever frame is shown;
+// under --temporal the stage runs once per displayed frame, so the exposure adapts across the frames.  --hdr PATH.pfm
+// (bt_write_pfm) saves the linear mean of the frame that is shown.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -101,6 +105,13 @@ struct Args {
     long frames = -1;                                     // -1: not given (1 with --temporal)
     bool has_camera_step = false;
     float camera_step[3] = {0.0f, 0.0f, 0.0f};
+    bool display = false;                                 // any of --tonemap, --exposure, --exposure-key, --exposure-adapt, --white
+    std::string tonemap = "aces";
+    bool exposure_auto = true;
+    float exposure_ev = 0.0f;
+    double exposure_key = -1.0;                           // -1: bt_display_params_default's, as the next two
+    float exposure_adapt = -1.0f, white = -1.0f;
+    std::string hdr;
 };
 
 void usage() {
@@ -118,7 +129,13 @@ void usage() {
                  "                             or --denoise-inline)\n"
                  "       [--temporal] [--frames N] [--camera-step X,Y,Z]   (extension: temporal accumulation with reprojection; N frames\n"
                  "                             of --samples each, the camera moved by X,Y,Z before each frame after the first;\n"
-                 "                             --output full only, not with --lens, --shard, --adaptive or --denoise-inline)\n");
+                 "                             --output full only, not with --lens, --shard, --adaptive or --denoise-inline)\n"
+                 "       [--tonemap clip|reinhard|aces] [--exposure auto|EV] [--exposure-key 0.18] [--exposure-adapt 1] [--white 4]\n"
+                 "                            (extension: display stage -- metered auto-exposure and a tone curve for the screenshot;\n"
+                 "                             under --temporal the exposure adapts from frame to frame; --output full only, not\n"
+                 "                             with --shard)\n"
+                 "       [--hdr PATH.pfm]     (extension: the linear mean of the shown frame as a Portable Float Map; --output full\n"
+                 "                             only, not with --shard)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -191,6 +208,32 @@ Args parse(int argc, char **argv) {
                 die("--camera-step expects X,Y,Z (finite)");
             a.has_camera_step = true;
         }
+        else if (k == "--tonemap") {
+            a.tonemap = val();
+            if (a.tonemap != "clip" && a.tonemap != "reinhard" && a.tonemap != "aces") die("--tonemap expects clip, reinhard or aces");
+            a.display = true;
+        }
+        else if (k == "--exposure") {
+            const std::string spec = val();
+            a.exposure_auto = spec == "auto";
+            if (!a.exposure_auto) {
+                char *end = nullptr;
+                a.exposure_ev = std::strtof(spec.c_str(), &end);
+                if (spec.empty() || *end != 0 || !(std::fabs(a.exposure_ev) < 3.0e38f)) die("--exposure expects auto or a finite EV");
+            }
+            a.display = true;
+        }
+        else if (k == "--exposure-key" || k == "--exposure-adapt" || k == "--white") {
+            const std::string spec = val();
+            char *end = nullptr;
+            const double f = std::strtod(spec.c_str(), &end);
+            const bool ok = !spec.empty() && *end == 0 && f > 0.0 && f < 3.0e38;
+            if (k == "--exposure-key") { if (!ok) die("--exposure-key expects a finite value > 0"); a.exposure_key = f; }
+            else if (k == "--exposure-adapt") { if (!ok || f > 1.0) die("--exposure-adapt expects a value in (0, 1]"); a.exposure_adapt = (float)f; }
+            else { if (!ok) die("--white expects a finite value > 0"); a.white = (float)f; }
+            a.display = true;
+        }
+        else if (k == "--hdr") a.hdr = val();
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -217,6 +260,10 @@ Args parse(int argc, char **argv) {
     if (a.temporal && a.denoise_inline) die("--temporal renders its own guides: use --denoise, not --denoise-inline");
     if (a.temporal && a.samples == 0) die("--temporal needs --samples >= 1 per frame");
     if (a.temporal && a.frames < 0) a.frames = 1;
+    if (a.display && a.output != "full") die("--tonemap and --exposure need --output full");
+    if (a.display && a.shard_world > 1) die("--tonemap and --exposure do not apply to a --shard run");
+    if (!a.hdr.empty() && a.output != "full") die("--hdr needs --output full");
+    if (!a.hdr.empty() && a.shard_world > 1) die("--hdr does not apply to a --shard run");
     return a;
 }
 
@@ -333,6 +380,20 @@ int main(int argc, char **argv) {
         check(bt_adaptive_resolve_device(adaptive, d_frame, d_mean, nullptr), "bt_adaptive_resolve_device");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     }
+    // --tonemap / --exposure (extension): the display stage replaces the plain preview
+    bt_display *display = nullptr;
+    bt_display_params dp;
+    bt_display_params_default(&dp);
+    if (args.display) {
+        display = bt_display_new();
+        if (!display) die(bt_last_error());
+        dp.tonemap = args.tonemap == "clip" ? BT_TONEMAP_CLIP : args.tonemap == "reinhard" ? BT_TONEMAP_REINHARD : BT_TONEMAP_ACES;
+        dp.auto_exposure = args.exposure_auto ? 1 : 0;
+        dp.ev = args.exposure_ev;
+        if (args.exposure_key > 0.0) dp.key = args.exposure_key;
+        if (args.exposure_adapt > 0.0f) dp.adapt = args.exposure_adapt;
+        if (args.white > 0.0f) dp.white = args.white;
+    }
     // --temporal (extension): one guided render into cleared frames and one accumulate per displayed frame
     bt_temporal *temporal = nullptr;
     double history_mean = 0.0, history_min = 0.0;
@@ -358,6 +419,9 @@ int main(int argc, char **argv) {
             check(bt_temporal_accumulate_device(temporal, &view, d_frame, args.samples * nn, d_guides[1], args.samples * nn, d_guides[2],
                                                 args.samples * nn, d_mean, nullptr, nullptr),
                   "bt_temporal_accumulate_device");
+            // every displayed frame passes the display stage; the last one does below, on the frame the screenshot shows
+            if (display && f + 1 < args.frames)
+                check(bt_display_device(display, d_mean, 1, d_rgba8, args.width, args.height, color_space, &dp, nullptr), "bt_display_device");
             hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
             const double delta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             sum_delta += delta;
@@ -427,7 +491,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "%.1f Msamples/s (render calls only)\n",
                  sum_delta > 0 ? (double)n_px * buffer_samples / sum_delta / 1e6 : 0.0);
 
-    if (!args.stats_json.empty()) {
+    auto write_stats = [&](const char *display_json) {
         FILE *f = std::fopen(args.stats_json.c_str(), "w");
         if (!f) die("cannot write " + args.stats_json);
         char ad[320] = "";
@@ -437,10 +501,11 @@ int main(int argc, char **argv) {
         if (args.temporal)
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
-        std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad);
+        std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s}\n", args.width,
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, display_json);
         std::fclose(f);
-    }
+    };
+    if (!args.stats_json.empty() && !display) write_stats("");        // with the display stage: once the frame has been shown
 
     // Ctrl+P (main.rs:275-298)
     std::string shot = args.screenshot;
@@ -532,9 +597,31 @@ int main(int argc, char **argv) {
         shown_samples = 1;                                  // the denoised buffer holds a mean
         std::fprintf(stderr, "denoised with guides of %u samples\n", gs);
     }
+    if (display) {
+        check(bt_display_device(display, d_shown, shown_samples, d_rgba8, args.width, args.height, color_space, &dp, nullptr), "bt_display_device");
+        float ev = 0.0f, mult = 0.0f;
+        uint32_t counters[258];
+        check(bt_display_exposure(display, &ev, &mult), "bt_display_exposure");
+        check(bt_debug_display_histogram(display, counters, 258), "bt_debug_display_histogram");
+        std::fprintf(stderr, "display: %s, exposure %s %+.4f EV (x %.5f), %u pixels under, %u over the metered range\n", args.tonemap.c_str(),
+                     args.exposure_auto ? "auto" : "manual", ev, mult, counters[256], counters[257]);
+        if (!args.stats_json.empty()) {
+            char dj[256];
+            std::snprintf(dj, sizeof dj, ", \"display\": {\"ev\": %.9g, \"mult\": %.9g, \"under\": %u, \"over\": %u, \"operator\": \"%s\"}", ev, mult,
+                          counters[256], counters[257], args.tonemap.c_str());
+            write_stats(dj);
+        }
+    }
+    if (!args.hdr.empty()) {
+        std::vector<float> lin(n_px * 4);
+        hip_check(hipMemcpy(lin.data(), d_shown, n_px * 16, hipMemcpyDeviceToHost), "hipMemcpy");
+        check(bt_write_pfm(args.hdr.c_str(), lin.data(), args.width, args.height, shown_samples), "bt_write_pfm");
+        std::fprintf(stderr, "saved linear frame to %s\n", args.hdr.c_str());
+    }
     if (!args.no_screenshot) {
-        check(bt_preview_device(d_shown, d_rgba8, args.width, args.height, shown_samples, color_space, nullptr),
-              "bt_preview_device");
+        if (!display)
+            check(bt_preview_device(d_shown, d_rgba8, args.width, args.height, shown_samples, color_space, nullptr),
+                  "bt_preview_device");
         std::vector<uint8_t> rgba8(n_px * 4);
         hip_check(hipMemcpy(rgba8.data(), d_rgba8, n_px * 4, hipMemcpyDeviceToHost), "hipMemcpy");
         check(bt_write_png(shot.c_str(), rgba8.data(), args.width, args.height), "bt_write_png");
@@ -552,6 +639,7 @@ int main(int argc, char **argv) {
     if (d_mean) (void)hipFree(d_mean);
     bt_adaptive_free(adaptive);
     bt_temporal_free(temporal);
+    bt_display_free(display);
     for (float *g : d_guides)
         if (g) (void)hipFree(g);
     bt_scene_free(scene);

@@ -606,6 +606,16 @@ int bt_write_png(const char *path, const uint8_t *rgba8, uint32_t width, uint32_
     }
 }
 
+int bt_write_pfm(const char *path, const float *rgba_host, uint32_t width, uint32_t height, uint32_t samples) {
+    if (!path || !rgba_host || width == 0 || height == 0 || samples == 0) return fail(BT_ERR_INVALID_ARG, "invalid argument");
+    try {
+        bt::write_pfm(path, rgba_host, width, height, samples);
+        return 0;
+    } catch (const bt::Error &e) {
+        return fail(e.code, e.message);
+    }
+}
+
 int bt_scene_find_by_tag(const bt_scene *scene, const char *tag, uint64_t *object_ref) {
     if (!scene || !tag || !object_ref) return fail(BT_ERR_INVALID_ARG, "null argument");
     for (const bt::Object &o : scene->scene.objects)

@@ -22,6 +22,21 @@ struct BtTemporalLaunch {
     float alpha_min, max_history, depth_tolerance, normal_min;
 };
 
+// The display stage (bt_display.hip).  A handle's device memory is uint32 words: the live counters (256 luminance bins, then
+// `under`, then `over`), the last call's counters for bt_debug_display_histogram, then one BtDisplayState.
+#define BT_DISPLAY_BINS 256
+#define BT_DISPLAY_COUNTERS 258
+#define BT_DISPLAY_STRIDE 260                // counters padded to 16 B
+struct BtDisplayState {
+    float e;                                 // the adapted exposure, meaningful while `valid`
+    uint32_t valid;
+    float shown_ev, shown_mult;              // what the last call's frame was shown with (bt_display_exposure)
+};
+struct BtDisplayExpose {
+    double log2_key;                         // log2(key), formed once on the host
+    float p_low, p_high, ev, ev_min, ev_max, adapt;
+};
+
 extern "C" {
 // bt_kernels.hip
 hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned grid, size_t lds_bytes, hipStream_t stream);
@@ -45,6 +60,12 @@ hipError_t bt_launch_denoise(const float *color, float nc, const float *albedo, 
                              float eps_albedo, hipStream_t stream);
 // bt_temporal.hip: mode 0 = no history, 1 = the previous view again, 2 = reproject
 hipError_t bt_launch_temporal(const BtTemporalLaunch *P, int mode, hipStream_t stream);
+// bt_display.hip: `op` is a bt_tonemap; `manual` != 0: the frame is shown with `ev`, the state's (e, valid) is not read
+hipError_t bt_launch_display_meter(const float *rgba, uint64_t n, uint32_t samples, uint32_t *live, hipStream_t stream);
+hipError_t bt_launch_display_expose(uint32_t *live, uint32_t *last, BtDisplayState *state, const BtDisplayExpose *p,
+                                    hipStream_t stream);
+hipError_t bt_launch_display_show(const float *rgba, uint8_t *out, uint64_t n, uint32_t samples, int color_space, int op,
+                                  float iw2, int manual, float ev, BtDisplayState *state, hipStream_t stream);
 // bt_api.cpp
 int bt_set_error_internal(int code, const char *msg);      // sets bt_last_error / bt_last_error_code; returns `code`
 int bt_scene_lens_on_internal(const bt_scene *scene);

@@ -1,6 +1,7 @@
 // bt_io.cpp -- the callers' side of the path: scene save (serde_json::to_writer_pretty
 // + optional gzip, main.rs:299-313), the built-in default scene (main.rs:107-214) and the PNG
-// screenshot of the 8-bit preview (main.rs:275-298).  No GPU work here.
+// screenshot of the 8-bit preview (main.rs:275-298), and the linear frame as a Portable Float Map (extension: bt_write_pfm).
+// No GPU work here.
 #include <zlib.h>
 
 #include <cmath>
@@ -250,6 +251,23 @@ void write_png(const std::string &path, const uint8_t *rgba, uint32_t w, uint32_
     chunk("IDAT", z.data(), (uint32_t)zlen);
     chunk("IEND", nullptr, 0);
     if (std::fclose(f) != 0) throw Error{BT_ERR_IO, "write error on " + path};
+}
+
+// EXTENSION, not in the reference: the linear mean as a colour PFM.  "PF", the size, a negative scale (= little-endian), then
+// the rows bottom to top, rgb * (1.0f / samples) as float32.
+void write_pfm(const std::string &path, const float *rgba, uint32_t w, uint32_t h, uint32_t samples) {
+    const float r = 1.0f / (float)samples;
+    std::vector<float> row((size_t)w * 3);
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw Error{BT_ERR_IO, "cannot create " + path};
+    bool ok = std::fprintf(f, "PF\n%u %u\n-1.0\n", w, h) > 0;
+    for (uint32_t y = h; y-- > 0 && ok;) {
+        const float *src = rgba + (size_t)y * w * 4;
+        for (uint32_t x = 0; x < w; ++x)
+            for (int c = 0; c < 3; ++c) row[(size_t)x * 3 + c] = src[(size_t)x * 4 + c] * r;
+        ok = std::fwrite(row.data(), sizeof(float), row.size(), f) == row.size();      // the hosts this library runs on are little-endian
+    }
+    if (std::fclose(f) != 0 || !ok) throw Error{BT_ERR_IO, "write error on " + path};
 }
 
 } // namespace bt

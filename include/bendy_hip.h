@@ -440,6 +440,70 @@ int bt_debug_temporal_history(bt_temporal *t, float *host, uint32_t n);
  * (z >= 1: at infinity) lies in `prev`: out = (x_f, y_f, z').  BT_ERR_INVALID_ARG for a view the accumulate would refuse. */
 int bt_debug_reproject(const bt_view *cur, const bt_view *prev, float x, float y, float z, float *out);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: display stage -- metered auto-exposure and tone mapping ----
+ * Buffer::preview divides by the sample count, applies the sRGB curve and saturates at 1.0.  This stage is off unless
+ * called, makes no parity claim and changes neither a render nor bt_preview*.  It meters the frame's luminance, derives an
+ * exposure on the device, adapts it from frame to frame and maps the exposed mean through a tone operator into RGBA8.
+ * The input is a frame of RGBA32F running sums with its sample count n (a mean is n = 1: what bt_denoise_device,
+ * bt_temporal_accumulate_device and bt_adaptive_resolve_device write).  Everything is float32 in the order written, without
+ * fused multiply-adds, with correctly rounded `/`:
+ *   meter, per pixel:  r = 1 / n;  c = rgb * r;  Y = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z;
+ *     !(Y >= 2^-16) -> `under` (zero, negatives, NaN);  else Y >= 2^16 -> `over` (+inf);  else bin (bits(Y) >> 20) - 888 of
+ *     256: eight bins per octave (the exponent and three mantissa bits) over 32 octaves.  The counts h_b are uint32.
+ *   expose, from the 256 counts (integers stay integers):  N = sum h_b;  lo = floor((double)p_low N);
+ *     hi = N - floor((double)p_high N);  P_b = the exclusive prefix sum;  w_b = max(0, min(P_b + h_b, hi) - max(P_b, lo));
+ *     W = sum w_b;  S = sum w_b (2 b + 1) (64-bit).  W == 0 (a black frame): the handle's state is left alone and the frame is
+ *     shown with the state's exposure if there is one, else with params.ev.  Otherwise m = S / (16.0 W) - 16.0 in float64
+ *     (the mean of the bin centres in log2), t = (float)(log2(key) - m) + ev with log2(key) formed once on the host in
+ *     float64, t clamped to [ev_min, ev_max]; state (e, valid): e = t if !valid or adapt >= 1, else e = e + (t - e) adapt;
+ *     valid = true.  mult = exp2(e) by the polynomial bt_preview's sRGB curve uses.
+ *     auto_exposure == 0: neither meter nor expose runs, e = ev, mult = exp2(ev), the state is untouched.
+ *   show, per pixel and channel:  x = c * mult;  BT_TONEMAP_CLIP: x;  the others first x = x > 0 ? x : 0, then
+ *     BT_TONEMAP_REINHARD: x (1 + x iw2) / (1 + x) with iw2 = 1 / (white white) formed on the host;
+ *     BT_TONEMAP_ACES (Narkowicz's fit): (x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14);
+ *     then the colour space (BT_COLOR_NONE / _LINEAR raw, _SRGB the sRGB curve) and the saturating conversion to 8 bits exactly
+ *     as bt_preview_device has them; alpha = the buffer's alpha, converted the same way.  BT_TONEMAP_CLIP with
+ *     auto_exposure == 0 and ev == 0 is bt_preview_device bit for bit. */
+typedef enum { BT_TONEMAP_CLIP = 0, BT_TONEMAP_REINHARD = 1, BT_TONEMAP_ACES = 2 } bt_tonemap;
+typedef struct {
+    double key;                /* > 0, finite: the luminance the metered mean is brought to (a double: log2(key) is float64) */
+    int32_t tonemap;           /* bt_tonemap */
+    int32_t auto_exposure;     /* 0: show with `ev`; else meter the frame, `ev` is a compensation added to the metered exposure */
+    float ev;                  /* finite; stops */
+    float p_low, p_high;       /* [0, 1), p_low + p_high < 1: the darkest / brightest fraction of the pixels the meter ignores */
+    float adapt;               /* (0, 1]: the fraction of the way to the new target one call moves; 1 = no memory */
+    float ev_min, ev_max;      /* ev_min <= ev_max: the metered exposure is clamped to this range */
+    float white;               /* > 0: BT_TONEMAP_REINHARD's white point, the exposed value that maps to 1 */
+} bt_display_params;
+typedef struct bt_display bt_display;     /* owns the counters and the adaptation state (2 KiB on the device); one stream at a time */
+/* ACES, auto_exposure 1, ev 0, key 0.18, p_low 0.10, p_high 0.02, adapt 1, ev_min -8, ev_max +8, white 4. */
+void bt_display_params_default(bt_display_params *out);
+/* No device work happens here: the handle allocates on its first bt_display_device, on the device current then. */
+bt_display *bt_display_new(void);
+void bt_display_free(bt_display *d);
+/* Forgets the adaptation state and the last call: the next metered frame sets the exposure outright. */
+int bt_display_reset(bt_display *d);
+/* Up to three kernels on `stream` (meter, expose, show; show alone with auto_exposure == 0); returns without synchronising,
+ * the exposure never visits the host.  `rgba_device`: width * height RGBA32F running sums of `samples` samples;
+ * `rgba8_device`: width * height RGBA8.  params == NULL: the defaults.  Checked before the device is touched, in this order,
+ * all BT_ERR_INVALID_ARG: NULL handle, input or output; samples == 0; zero width or height (or 2^32 pixels and more); input
+ * equal to output; a colour space other than BT_COLOR_NONE / _LINEAR / _SRGB (BT_COLOR_NORMAL is for the normal AOV); an
+ * unknown operator; non-finite ev; key <= 0 or non-finite; p_low or p_high outside [0, 1) or p_low + p_high >= 1; adapt
+ * outside (0, 1]; ev_min > ev_max (or either NaN); white <= 0 (or NaN).  A valid call without a device returns BT_ERR_DEVICE.
+ * Not provided: a host-buffer variant, sharded frames, metering regions or weights, per-luminance (hue-preserving)
+ * operators and dithering. */
+int bt_display_device(bt_display *d, const float *rgba_device, uint32_t samples, uint8_t *rgba8_device, uint32_t width,
+                      uint32_t height, int32_t color_space, const bt_display_params *params, void *stream);
+/* The exposure the last bt_display_device showed its frame with, in stops, and its multiplier (synchronises).  Either
+ * pointer may be NULL.  BT_ERR_INVALID_ARG while there is none: before the first call and after bt_display_reset. */
+int bt_display_exposure(bt_display *d, float *ev, float *mult);
+/* For tests: the counters of the last metered call -- 256 bins, then `under`, then `over` (258 in all); zeros while there is
+ * none.  n == 0 returns 258, else up to n are copied to `host` (synchronises) and the number copied is returned. */
+int bt_debug_display_histogram(bt_display *d, uint32_t *host, uint32_t n);
+/* The linear frame as a Portable Float Map: "PF\n<width> <height>\n-1.0\n", then the rows bottom to top, per pixel
+ * rgb * (1.0f / samples) as little-endian float32.  `rgba_host` is the frame of running sums on the host. */
+int bt_write_pfm(const char *path, const float *rgba_host, uint32_t width, uint32_t height, uint32_t samples);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);
