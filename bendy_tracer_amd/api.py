@@ -193,7 +193,8 @@ EXPORTS = [
     "bt_scene_camera_view", "bt_scene_set_camera_pose", "bt_temporal_params_default", "bt_temporal_new", "bt_temporal_free",
     "bt_temporal_reset", "bt_temporal_accumulate_device", "bt_debug_temporal_history", "bt_debug_reproject",
     "bt_display_params_default", "bt_display_new", "bt_display_free", "bt_display_reset", "bt_display_device",
-    "bt_display_exposure", "bt_debug_display_histogram", "bt_write_pfm",
+    "bt_display_exposure", "bt_debug_display_histogram", "bt_write_pfm", "bt_scene_export_sorted_rows",
+    "bt_debug_abs_limit",
 ]
 
 
@@ -231,6 +232,9 @@ def _load():
     L.bt_scene_object_count.argtypes = [vp]
     L.bt_scene_data_count.argtypes = [vp]
     L.bt_scene_export_prims.argtypes = [vp, fp, C.c_int]
+    L.bt_scene_export_sorted_rows.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int]
+    L.bt_debug_abs_limit.restype = C.c_float
+    L.bt_debug_abs_limit.argtypes = [C.c_float]
     L.bt_debug_primary_mask.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32]
     L.bt_debug_set_object.argtypes = [vp, C.c_uint64, fp, C.c_float]
@@ -428,6 +432,24 @@ class Scene:
         out = np.zeros(n, dtype=np.float32)
         _check(lib.bt_scene_export_prims(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n))
         return out.reshape(-1, 36)
+
+    AAN_ROW = np.dtype([("it_a", "<f4"), ("it_b", "<f4"), ("lim_a", "<f4"), ("lim_b", "<f4"), ("t_w", "<f4"),
+                        ("sgn_mask", "<u4"), ("prio", "<u4"), ("pad", "<u4")])                       # bt_types.h BtRectAAN
+    LA_ROW = np.dtype([("n", "<f4", 3), ("first_of_normal", "<u4"), ("t", "<f4", 3), ("prio", "<u4"), ("a_x", "<f4", 2),
+                       ("a_y", "<f4", 2), ("a_z", "<f4", 2), ("a_w", "<f4", 2), ("lim", "<f4", 2), ("pad", "<u4", 2)])  # BtRectLA
+
+    def export_sorted_rows(self):
+        """bt_scene_export_sorted_rows (tests): the sorted view of the primitive table exactly as uploaded to the GPU --
+        {"n_aan": int32 [3], "aan": AAN_ROW records, "la": LA_ROW records, "other": int32 rows of export_prims()}."""
+        n = _check(lib.bt_scene_export_sorted_rows(self._h, None, 0))
+        w = np.zeros(n, dtype=np.uint32)
+        _check(lib.bt_scene_export_sorted_rows(self._h, w.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        n_aan, n_la, n_other = w[:3].astype(np.int32), int(w[3]), int(w[4])
+        a0, l0 = 5, 5 + 8 * int(n_aan.sum())
+        o0 = l0 + 20 * n_la
+        assert o0 + n_other == n
+        return {"n_aan": n_aan, "aan": w[a0:l0].view(self.AAN_ROW), "la": w[l0:o0].view(self.LA_ROW),
+                "other": w[o0:].view(np.int32)}
 
     def set_tuning(self, **knobs):
         """bt_scene_set_tuning: pins launch-shape knobs of this handle (tests and A/B tools; none of them changes a

@@ -663,6 +663,34 @@ int bt_scene_export_prims(const bt_scene *scene, float *out, int cap) {
     return total;
 }
 
+// TEST INFRASTRUCTURE: the sorted view of the table (bt_scene.cpp flatten_scene, bt_device.hpp intersect_sorted) as one
+// run of 32-bit words: n_aan[3], n_la, n_other, then the BtRectAAN rows (8 words each), the BtRectLA rows (20 words each)
+// and other_rows, each exactly as uploaded
+int bt_scene_export_sorted_rows(const bt_scene *scene, uint32_t *out, int cap) {
+    if (!scene) return fail(BT_ERR_INVALID_ARG, "null scene");
+    bt_scene *s = const_cast<bt_scene *>(scene);
+    int rc = ensure_flat(s);
+    if (rc) return rc;
+    const bt::FlatScene &f = s->flat;
+    std::vector<uint32_t> words(5);
+    for (int a = 0; a < 3; ++a) words[a] = (uint32_t)f.n_aan[a];
+    words[3] = (uint32_t)f.la_rows.size();
+    words[4] = (uint32_t)f.other_rows.size();
+    auto append = [&words](const void *p, size_t bytes) {
+        const size_t at = words.size();
+        words.resize(at + bytes / 4);
+        if (bytes) std::memcpy(words.data() + at, p, bytes);
+    };
+    append(f.aan_rows.data(), sizeof(BtRectAAN) * f.aan_rows.size());
+    append(f.la_rows.data(), sizeof(BtRectLA) * f.la_rows.size());
+    append(f.other_rows.data(), sizeof(int32_t) * f.other_rows.size());
+    const int total = (int)words.size();
+    if (out && cap > 0) std::memcpy(out, words.data(), sizeof(uint32_t) * (size_t)std::min(cap, total));
+    return total;
+}
+
+float bt_debug_abs_limit(float limit) { return bt::abs_limit(limit); }
+
 int bt_debug_set_object(bt_scene *scene, uint64_t object_ref, const float *translation, float radius) {
     if (!scene) return fail(BT_ERR_INVALID_ARG, "null scene");
     const int i = scene->scene.object_index(object_ref);

@@ -269,6 +269,29 @@ size_t FlatScene::lds_bytes() const {
     return (n + 15) & ~(size_t)15;
 }
 
+// Rect::contains_point tests `x * x <= L` (rect.rs:74-80).  x -> fl(x * x) is monotone in |x| (rounding and underflow
+// included), so the set of x that pass is |x| <= s for the largest float s with fl(s * s) <= L: found here by bisection
+// over the bit patterns, with the same IEEE multiplication the kernel would perform.  (L negative or NaN: nothing
+// passes, s = -1.)
+float abs_limit(float L) {
+    if (!(L >= 0.0f)) return -1.0f;
+    uint32_t lo = 0u, hi = 0x7f800000u;                 // fl(0 * 0) = 0 <= L holds
+    auto passes = [L](uint32_t bits) {
+        float x;
+        std::memcpy(&x, &bits, 4);
+        volatile float sq = x * x;
+        return sq <= L;
+    };
+    if (passes(hi)) return std::numeric_limits<float>::infinity();
+    while (hi - lo > 1u) {                              // passes(lo) && !passes(hi)
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (passes(mid)) lo = mid; else hi = mid;
+    }
+    float s;
+    std::memcpy(&s, &lo, 4);
+    return s;
+}
+
 FlatScene flatten_scene(const Scene &sc) {
     FlatScene fs;
     // data -> materials / volumes
@@ -442,29 +465,8 @@ FlatScene flatten_scene(const Scene &sc) {
         fs.root_albedo = shade_color;
         fs.root_color = add(shade_color, m.emitted);  // color_data.color += emitted (mod.rs:450)
     }
-    // sorted view of the table for bt_device.hpp intersect_sorted()
-    // Rect::contains_point tests `x * x <= L` (rect.rs:74-80).  x -> fl(x * x) is monotone in |x| (rounding and underflow
-    // included), so the set of x that pass is |x| <= s for the largest float s with fl(s * s) <= L: found here by bisection
-    // over the bit patterns, with the same IEEE multiplication the kernel would perform.  The sorted rows carry s; the
-    // kernel compares |x| with it and saves the multiplication.  (L negative or NaN: nothing passes, s = -1.)
-    auto abs_limit = [](float L) -> float {
-        if (!(L >= 0.0f)) return -1.0f;
-        uint32_t lo = 0u, hi = 0x7f800000u;                 // fl(0 * 0) = 0 <= L holds
-        auto passes = [L](uint32_t bits) {
-            float x;
-            std::memcpy(&x, &bits, 4);
-            volatile float sq = x * x;
-            return sq <= L;
-        };
-        if (passes(hi)) return std::numeric_limits<float>::infinity();
-        while (hi - lo > 1u) {                              // passes(lo) && !passes(hi)
-            const uint32_t mid = lo + (hi - lo) / 2u;
-            if (passes(mid)) lo = mid; else hi = mid;
-        }
-        float s;
-        std::memcpy(&s, &lo, 4);
-        return s;
-    };
+    // sorted view of the table for bt_device.hpp intersect_sorted(); the rows carry abs_limit() of the squared half
+    // extents, the kernel compares |x| with it and saves the multiplication
     for (int axis = 0; axis < 3; ++axis)
         for (size_t i = 0; i < fs.prims.size(); ++i) {
             const BtPrim &p = fs.prims[i];

@@ -88,6 +88,9 @@ struct FlatScene {
     size_t lds_bytes() const;
 };
 FlatScene flatten_scene(const Scene &scene);
+// the sorted rows' form of Rect::contains_point's `x * x <= L` (rect.rs:74-80): the largest s with fl(s * s) <= L, so
+// that the test is |x| <= s; -1 (nothing passes) for a negative or NaN L
+float abs_limit(float L);
 
 // ---- bt_io.cpp: the callers' side ----
 std::string format_f32(float v);

@@ -86,7 +86,9 @@ struct BtRectAAN {
 };
 static_assert(sizeof(BtRectAAN) == 32, "BtRectAAN must be 32 bytes");
 // ... and the BT_PRIM_RECT_LA rows (every cuboid face under a rotation), rows with bitwise equal normals next to each
-// other: opposite faces of a cuboid share the normal (cuboid.rs:19-30), hence q = dot(d, n) and its reciprocal.  The two
+// other: they share q = dot(d, n) and its reciprocal.  Opposite faces of ONE cuboid have opposite normals (cuboid.rs:19-30),
+// so a run longer than one row needs two objects under the same matrix: none of the bundled scenes has one
+// (DESIGN.md 5.6), tests/rect_scenes.py builds them.  The two
 // rows of `M^-1 | t'` that the containment test needs sit side by side as pairs for packed arithmetic.
 struct BtRectLA {
     BtV3 n;                 // world normal c = M * z

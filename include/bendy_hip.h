@@ -158,6 +158,15 @@ int bt_scene_data_count(const bt_scene *scene);
 /* Flattened primitive table as uploaded to the GPU, for loader cross-checks:
  * writes up to `cap` floats, returns the number available. */
 int bt_scene_export_prims(const bt_scene *scene, float *out, int cap);
+/* For tests: the sorted view of that table which rect scenes without volumes are intersected through, as
+ * uploaded, in 32-bit words: n_aan[3] (x-, y-, z-normal rows), n_la, n_other, then the axis-aligned rows (8 words each:
+ * it_a, it_b, lim_a, lim_b, t_w, sgn_mask, prio, pad), the rows of rects with axis-aligned local axes (20 words each:
+ * n[3], first_of_normal, t[3], prio, a_x[2], a_y[2], a_z[2], a_w[2], lim[2], pad[2]) and the indices of every other row
+ * of the primitive table.  Writes up to `cap` words (out may be NULL), returns the number available. */
+int bt_scene_export_sorted_rows(const bt_scene *scene, uint32_t *out, int cap);
+/* For tests: the limit those rows carry for a squared half extent `limit` -- the largest s with fl(s * s) <= limit, so
+ * that Rect::contains_point's `x * x <= limit` (rect.rs:74-80) is |x| <= s; -1 for a negative or NaN limit. */
+float bt_debug_abs_limit(float limit);
 /* For tests: the per-block sphere masks of the sphere-only build without volumes, computed on the host
  * by the mask kernel's own code.  Blocks of a launch with `slices` (1, 2, 4, ..., 32) blocks per 16x16 tile, in launch order:
  * tile-major over the frame, or over rank `rank`'s tiles when world > 1.  Bit i set = sphere row i may be hit by a primary
