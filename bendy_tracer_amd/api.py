@@ -172,6 +172,10 @@ class _CDisplayParams(C.Structure):  # include/bendy_hip.h `bt_display_params` (
                 ("p_high", C.c_float), ("adapt", C.c_float), ("ev_min", C.c_float), ("ev_max", C.c_float), ("white", C.c_float)]
 
 
+class _CGlareParams(C.Structure):  # include/bendy_hip.h `bt_glare_params` (extension)
+    _fields_ = [("levels", C.c_uint32), ("spread", C.c_float), ("strength", C.c_float), ("max_value", C.c_float)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -195,6 +199,7 @@ EXPORTS = [
     "bt_display_params_default", "bt_display_new", "bt_display_free", "bt_display_reset", "bt_display_device",
     "bt_display_exposure", "bt_debug_display_histogram", "bt_write_pfm", "bt_scene_export_sorted_rows",
     "bt_debug_abs_limit",
+    "bt_glare_params_default", "bt_glare_new", "bt_glare_free", "bt_glare_device", "bt_debug_glare_plane", "bt_debug_glare_host",
 ]
 
 
@@ -310,6 +315,13 @@ def _load():
     L.bt_display_exposure.argtypes = [vp, fp, fp]
     L.bt_debug_display_histogram.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32]
     L.bt_write_pfm.argtypes = [C.c_char_p, fp, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.bt_glare_params_default.argtypes = [C.POINTER(_CGlareParams)]
+    L.bt_glare_new.restype = vp
+    L.bt_glare_new.argtypes = []
+    L.bt_glare_free.argtypes = [vp]
+    L.bt_glare_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(_CGlareParams), vp]
+    L.bt_debug_glare_plane.argtypes = [vp, C.c_uint32, fp, C.c_uint32]
+    L.bt_debug_glare_host.argtypes = [fp, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.POINTER(_CGlareParams)]
     return L
 
 
@@ -1101,6 +1113,94 @@ class Display:
         out = np.zeros(258, dtype=np.uint32)
         _check(lib.bt_debug_display_histogram(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), 258))
         return out[:256].copy(), int(out[256]), int(out[257])
+
+
+def _glare_defaults():
+    p = _CGlareParams()
+    lib.bt_glare_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class GlareParams:
+    """`bt_glare_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_glare_params_default's value."""
+    levels: Optional[int] = None
+    spread: Optional[float] = None
+    strength: Optional[float] = None
+    max_value: Optional[float] = None
+
+    def __post_init__(self):
+        d = _glare_defaults()
+        for k, _ in _CGlareParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+
+    def _c(self):
+        return _CGlareParams(int(self.levels), float(self.spread), float(self.strength), float(self.max_value))
+
+
+class Glare:
+    """`bt_glare` (include/bendy_hip.h): EXTENSION, not in the reference -- the glare stage: an energy-conserving bloom in
+    scene-linear light, ahead of the display stage.  The handle owns the pyramid on the device (< 5.4 B per
+    pixel, grown on demand).  Keywords = GlareParams fields."""
+
+    def __init__(self, **params):
+        self.params = GlareParams(**params)
+        h = lib.bt_glare_new()
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_glare_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def apply(self, buffer: Buffer, *, out: Optional[Buffer] = None, **params) -> Buffer:
+        """The frame of `buffer` (running sums of `.samples` samples, or a mean with samples = 1) with the glare added -> a
+        Buffer holding the MEAN (samples = 1), as `denoise` returns.  Keywords override the handle's GlareParams for this
+        call."""
+        p = GlareParams(**{**{k: getattr(self.params, k) for k, _ in _CGlareParams._fields_}, **params})
+        if buffer.device == "cpu":
+            raise BendyError(-1, "apply needs a device-resident buffer (there is no host-buffer variant)")
+        import torch
+        if out is None:
+            out = Buffer(buffer.width, buffer.height, buffer.color_space, device=buffer.device)
+        elif (out.width, out.height) != (buffer.width, buffer.height) or out.device == "cpu" or out.data.device != buffer.data.device:
+            raise BendyError(-1, f"out must be a {buffer.width}x{buffer.height} buffer on the input's device")
+        out.color_space = buffer.color_space
+        cp = p._c()
+        self._dims = (buffer.width, buffer.height)
+        _check(lib.bt_glare_device(self._h, buffer.data.data_ptr(), max(buffer.samples, 1), out.data.data_ptr(), buffer.width,
+                                   buffer.height, C.byref(cp), torch.cuda.current_stream().cuda_stream))
+        out.samples = 1
+        return out
+
+    def plane(self, level):
+        """bt_debug_glare_plane (tests; synchronises): A_level of the last `apply` as float32 [h_k, w_k, 4]."""
+        n = _check(lib.bt_debug_glare_plane(self._h, int(level), None, 0))
+        flat = np.zeros(n, dtype=np.float32)
+        _check(lib.bt_debug_glare_plane(self._h, int(level), flat.ctypes.data_as(C.POINTER(C.c_float)), n))
+        w, h = self._dims
+        for _ in range(int(level)):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        return flat.reshape(h, w, 4)
+
+
+def glare_host(array, samples=1, **params):
+    """bt_debug_glare_host (tests, no device): the whole glare stage on the host through csrc/bt_glare.hpp's own functions.
+    `array`: float32 [H, W, 4] running sums -> the glared mean, float32 [H, W, 4]."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise BendyError(-1, "glare_host expects a [H, W, 4] array")
+    out = np.empty_like(a)
+    cp = GlareParams(**params)._c()
+    _check(lib.bt_debug_glare_host(a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                   a.shape[1], a.shape[0], C.byref(cp)))
+    return out
 
 
 _default_denoiser = None

@@ -24,6 +24,9 @@
 // with any of them the screenshot comes from bt_display_device instead of bt_preview_device, applied to whatever frame is shown;
 // under --temporal the stage runs once per displayed frame, so the exposure adapts across the frames.  --hdr PATH.pfm
 // (bt_write_pfm) saves the linear mean of the frame that is shown.
+// --glare STRENGTH [--glare-levels N] [--glare-spread X] (extension too; bt_glare): the mean that is about to be shown (plain,
+// denoised, adaptive-resolved or temporal) passes bt_glare_device first, ahead of bt_display_device or bt_preview_device; under
+// --temporal once per displayed frame.  --hdr then holds the glared mean, because that is what is shown.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -112,6 +115,9 @@ struct Args {
     double exposure_key = -1.0;                           // -1: bt_display_params_default's, as the next two
     float exposure_adapt = -1.0f, white = -1.0f;
     std::string hdr;
+    bool glare = false;
+    float glare_strength = 0.0f, glare_spread = -1.0f;   // -1: bt_glare_params_default's, as the levels
+    long glare_levels = -1;
 };
 
 void usage() {
@@ -135,7 +141,10 @@ void usage() {
                  "                             under --temporal the exposure adapts from frame to frame; --output full only, not\n"
                  "                             with --shard)\n"
                  "       [--hdr PATH.pfm]     (extension: the linear mean of the shown frame as a Portable Float Map; --output full\n"
-                 "                             only, not with --shard)\n");
+                 "                             only, not with --shard)\n"
+                 "       [--glare STRENGTH] [--glare-levels 6] [--glare-spread 1]   (extension: glare stage -- an energy-conserving bloom\n"
+                 "                             on the mean that is shown, ahead of the display stage or the preview; --hdr then holds\n"
+                 "                             the glared mean; --output full only, not with --shard)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -234,6 +243,26 @@ Args parse(int argc, char **argv) {
             a.display = true;
         }
         else if (k == "--hdr") a.hdr = val();
+        else if (k == "--glare" || k == "--glare-spread") {
+            const std::string spec = val();
+            char *end = nullptr;
+            const float f = std::strtof(spec.c_str(), &end);
+            const bool ok = !spec.empty() && *end == 0;
+            if (k == "--glare") {
+                if (!ok || !(f >= 0.0f && f <= 1.0f)) die("--glare expects a strength in [0, 1]");
+                a.glare_strength = f;
+                a.glare = true;
+            } else {
+                if (!ok || !(f > 0.0f && f <= 16.0f)) die("--glare-spread expects a value in (0, 16]");
+                a.glare_spread = f;
+            }
+        }
+        else if (k == "--glare-levels") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.glare_levels = std::strtol(spec.c_str(), &end, 10);
+            if (spec.empty() || *end != 0 || a.glare_levels < 0 || a.glare_levels > 16) die("--glare-levels expects a count in 0 .. 16");
+        }
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -264,6 +293,9 @@ Args parse(int argc, char **argv) {
     if (a.display && a.shard_world > 1) die("--tonemap and --exposure do not apply to a --shard run");
     if (!a.hdr.empty() && a.output != "full") die("--hdr needs --output full");
     if (!a.hdr.empty() && a.shard_world > 1) die("--hdr does not apply to a --shard run");
+    if (!a.glare && (a.glare_levels >= 0 || a.glare_spread > 0.0f)) die("--glare-levels and --glare-spread need --glare");
+    if (a.glare && a.output != "full") die("--glare needs --output full");
+    if (a.glare && a.shard_world > 1) die("--glare does not apply to a --shard run");
     return a;
 }
 
@@ -394,6 +426,27 @@ int main(int argc, char **argv) {
         if (args.exposure_adapt > 0.0f) dp.adapt = args.exposure_adapt;
         if (args.white > 0.0f) dp.white = args.white;
     }
+    // --glare (extension): the mean that is shown passes the glare stage first
+    bt_glare *glare = nullptr;
+    bt_glare_params gp;
+    bt_glare_params_default(&gp);
+    float *d_glare = nullptr;                              // the glared mean
+    std::string glare_json;
+    uint32_t glare_levels = 0;                             // the effective number: bt_glare_device's step 2
+    if (args.glare) {
+        glare = bt_glare_new();
+        if (!glare) die(bt_last_error());
+        gp.strength = args.glare_strength;
+        if (args.glare_levels >= 0) gp.levels = (uint32_t)args.glare_levels;
+        if (args.glare_spread > 0.0f) gp.spread = args.glare_spread;
+        hip_check(hipMalloc((void **)&d_glare, n_px * 16), "hipMalloc");
+        for (uint32_t m = std::max(args.width, args.height) - 1; m; m >>= 1) ++glare_levels;
+        glare_levels = std::min(glare_levels, gp.levels);
+        char gj[160];
+        std::snprintf(gj, sizeof gj, ", \"glare\": {\"strength\": %.9g, \"levels\": %u, \"spread\": %.9g}", gp.strength,
+                      glare_levels, gp.spread);
+        glare_json = gj;
+    }
     // --temporal (extension): one guided render into cleared frames and one accumulate per displayed frame
     bt_temporal *temporal = nullptr;
     double history_mean = 0.0, history_min = 0.0;
@@ -419,9 +472,12 @@ int main(int argc, char **argv) {
             check(bt_temporal_accumulate_device(temporal, &view, d_frame, args.samples * nn, d_guides[1], args.samples * nn, d_guides[2],
                                                 args.samples * nn, d_mean, nullptr, nullptr),
                   "bt_temporal_accumulate_device");
-            // every displayed frame passes the display stage; the last one does below, on the frame the screenshot shows
+            // every displayed frame passes the glare and the display stage; the last one does below, on the frame the screenshot shows
+            if (glare && f + 1 < args.frames)
+                check(bt_glare_device(glare, d_mean, 1, d_glare, args.width, args.height, &gp, nullptr), "bt_glare_device");
             if (display && f + 1 < args.frames)
-                check(bt_display_device(display, d_mean, 1, d_rgba8, args.width, args.height, color_space, &dp, nullptr), "bt_display_device");
+                check(bt_display_device(display, glare ? d_glare : d_mean, 1, d_rgba8, args.width, args.height, color_space, &dp, nullptr),
+                      "bt_display_device");
             hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
             const double delta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             sum_delta += delta;
@@ -501,8 +557,8 @@ int main(int argc, char **argv) {
         if (args.temporal)
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
-        std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, display_json);
+        std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s%s}\n", args.width,
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, glare_json.c_str(), display_json);
         std::fclose(f);
     };
     if (!args.stats_json.empty() && !display) write_stats("");        // with the display stage: once the frame has been shown
@@ -597,6 +653,13 @@ int main(int argc, char **argv) {
         shown_samples = 1;                                  // the denoised buffer holds a mean
         std::fprintf(stderr, "denoised with guides of %u samples\n", gs);
     }
+    if (glare) {
+        check(bt_glare_device(glare, d_shown, shown_samples, d_glare, args.width, args.height, &gp, nullptr), "bt_glare_device");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        d_shown = d_glare;
+        shown_samples = 1;                                  // the glared buffer holds a mean
+        std::fprintf(stderr, "glare: strength %g over %u levels, spread %g\n", gp.strength, glare_levels, gp.spread);
+    }
     if (display) {
         check(bt_display_device(display, d_shown, shown_samples, d_rgba8, args.width, args.height, color_space, &dp, nullptr), "bt_display_device");
         float ev = 0.0f, mult = 0.0f;
@@ -640,6 +703,8 @@ int main(int argc, char **argv) {
     bt_adaptive_free(adaptive);
     bt_temporal_free(temporal);
     bt_display_free(display);
+    bt_glare_free(glare);
+    if (d_glare) (void)hipFree(d_glare);
     for (float *g : d_guides)
         if (g) (void)hipFree(g);
     bt_scene_free(scene);

@@ -513,6 +513,58 @@ int bt_debug_display_histogram(bt_display *d, uint32_t *host, uint32_t n);
  * rgb * (1.0f / samples) as little-endian float32.  `rgba_host` is the frame of running sums on the host. */
 int bt_write_pfm(const char *path, const float *rgba_host, uint32_t width, uint32_t height, uint32_t samples);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: glare stage -- an energy-conserving bloom ahead of the display stage ----
+ * The tone curve maps every emitter far above 1.0 to the same flat white.  Glare is light scattered in the eye or the lens: a
+ * wide point-spread function applied in scene-linear light, before exposure and tone mapping.  This stage is off unless
+ * called, makes no parity claim and changes neither a render nor bt_preview* nor bt_display_*.  The input is a frame of
+ * RGBA32F running sums with its sample count n (a mean is n = 1); the output is a MEAN, as bt_denoise_device's is: preview or
+ * display it with samples = 1.  Everything is float32 in the order written, without fused multiply-adds, with correctly
+ * rounded `/` (csrc/bt_glare.hpp has the same lines as code; tests/glare_ref.py in numpy):
+ *   1. sanitise, per pixel and channel:  r = 1 / n;  c = rgb * r;  s = c >= 0 ? c : 0 (NaN and negatives -> 0);
+ *      s = s < max_value ? s : max_value (+inf and fireflies are capped).  The planes below carry rgb and a fourth channel of 0.
+ *   2. L = min(levels, bit_length(max(width, height) - 1)); level k has sides ceil(side_{k-1} / 2);  D_0 = s.
+ *   3. down, k = 1 .. L, separable, x then y.  Per axis, output i takes the taps a, b, c, d at 2i-1, 2i, 2i+1, 2i+2, each
+ *      clamped to [0, side_{k-1} - 1]:  t = b + c;  D = (((a + d) + t) + (t + t)) * 0.125     (the binomial [1 3 3 1] / 8)
+ *   4. weights, on the host in float64 by repeated multiplication:  p_1 = 1, p_k = p_{k-1} * (double)spread, S their sum in
+ *      order, w_k = (float)(p_k / S).
+ *   5. up:  A_L = D_L * w_L;  for k = L-1 .. 1:  A_k = D_k * w_k + up(A_{k+1}).  up is separable, x then y.  Per axis, output
+ *      x takes near = x >> 1 and far = near - 1 (x even) or near + 1 (x odd), both clamped to the coarser side:
+ *      ((far + near) + (near + near)) * 0.25                                                 (the tent [1 3] / 4)
+ *   6. composite, per pixel:  G = up(A_1);  out.rgb = s + (G - s) * strength;  out.a = the input's a.
+ *   7. L = 0 (levels = 0 or a 1 x 1 frame):  out.rgb = s.
+ * The filter is linear and non-negative and each level's weights sum to 1 away from the border, so an impulse keeps its
+ * energy.  There is no brightness threshold and no dependence on exposure: the stage commutes with the exposure multiplier. */
+typedef struct {
+    uint32_t levels;           /* <= 16; the effective number is limited by the frame (step 2) */
+    float spread;              /* (0, 16], finite: each coarser level weighs `spread` times the one before */
+    float strength;            /* [0, 1]: the fraction of the light that is scattered */
+    float max_value;           /* > 0, finite: the cap of step 1 */
+} bt_glare_params;
+typedef struct bt_glare bt_glare;         /* owns the pyramid: float4 planes, < 5.4 B per pixel (A_k overwrites D_k); one stream at a time */
+/* levels 6, spread 1, strength 0.08, max_value 65536 (the display meter's `over` boundary).  Starting values, not tuned. */
+void bt_glare_params_default(bt_glare_params *out);
+/* No device work happens here: the handle allocates on its first bt_glare_device, on the device current then, and grows on
+ * demand. */
+bt_glare *bt_glare_new(void);
+void bt_glare_free(bt_glare *g);
+/* 2 L kernels on `stream` (one for L = 0); returns without synchronising.  `rgba_device`: width * height RGBA32F running sums of
+ * `samples` samples; `out_device`: width * height RGBA32F, the glared mean.  params == NULL: the defaults.  Checked before
+ * the device is touched, in this order, all BT_ERR_INVALID_ARG: NULL handle, input or output; samples == 0; zero width or
+ * height (or 2^32 pixels and more); output equal to input; levels > 16; spread not finite or outside (0, 16]; strength outside
+ * [0, 1] (or NaN); max_value not finite or <= 0.  A valid call without a device returns BT_ERR_DEVICE, and so does a frame
+ * whose 16 x 16 tiles do not fit one launch (2^24 tiles and more).
+ * Not provided: host buffers, sharded frames, anisotropic or spectral point-spread functions, a brightness threshold. */
+int bt_glare_device(bt_glare *g, const float *rgba_device, uint32_t samples, float *out_device, uint32_t width, uint32_t height,
+                    const bt_glare_params *params, void *stream);
+/* For tests: plane A_k (k = 1 .. L of the last call) as RGBA float, the fourth channel 0.  n == 0 returns the element count,
+ * else up to n floats are copied to `host` (synchronises) and the number copied is returned.  BT_ERR_INVALID_ARG for a
+ * level the last call did not have. */
+int bt_debug_glare_plane(bt_glare *g, uint32_t level, float *host, uint32_t n);
+/* For tests, no device: the whole definition on the host through csrc/bt_glare.hpp's own functions.  The same checks as
+ * bt_glare_device without the handle. */
+int bt_debug_glare_host(const float *rgba_host, uint32_t samples, float *out_host, uint32_t width, uint32_t height,
+                        const bt_glare_params *params);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);

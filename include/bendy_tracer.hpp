@@ -151,4 +151,23 @@ class Tracer {                                          // mod.rs:165-203
     }
 };
 
+// EXTENSION, not in the reference: a thin delegate of the glare stage (bt_glare in bendy_hip.h) -- an
+// energy-conserving bloom on device-resident frames, ahead of bt_display_device or bt_preview_device.  `out` receives a MEAN:
+// preview or display it with samples = 1.
+class Glare {
+  public:
+    bt_glare_params params;
+    Glare() : h_(bt_glare_new()) { if (!h_) throw Error(bt_last_error_code(), bt_last_error()); bt_glare_params_default(&params); }
+    Glare(const Glare &) = delete;
+    Glare &operator=(const Glare &) = delete;
+    ~Glare() { bt_glare_free(h_); }
+    void apply(const float *rgba_device, unsigned samples, float *out_device, unsigned width, unsigned height, void *stream = nullptr) {
+        check(bt_glare_device(h_, rgba_device, samples, out_device, width, height, &params, stream));
+    }
+    bt_glare *handle() const { return h_; }
+
+  private:
+    bt_glare *h_;
+};
+
 } // namespace bendy
