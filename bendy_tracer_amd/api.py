@@ -51,6 +51,13 @@ class Tonemap(enum.IntEnum):  # include/bendy_hip.h `bt_tonemap` (extension)
     Aces = 2
 
 
+class Filter(enum.IntEnum):  # include/bendy_hip.h `bt_resample_filter` (extension)
+    Box = 0
+    Tent = 1
+    Mitchell = 2
+    Lanczos3 = 3
+
+
 class Status(enum.IntEnum):  # tracer/mod.rs:159-163
     Done = 0
     InProgress = 1
@@ -176,6 +183,10 @@ class _CGlareParams(C.Structure):  # include/bendy_hip.h `bt_glare_params` (exte
     _fields_ = [("levels", C.c_uint32), ("spread", C.c_float), ("strength", C.c_float), ("max_value", C.c_float)]
 
 
+class _CResampleParams(C.Structure):  # include/bendy_hip.h `bt_resample_params` (extension)
+    _fields_ = [("filter", C.c_int32), ("max_value", C.c_float), ("clamp_negative", C.c_int32)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -200,6 +211,8 @@ EXPORTS = [
     "bt_display_exposure", "bt_debug_display_histogram", "bt_write_pfm", "bt_scene_export_sorted_rows",
     "bt_debug_abs_limit",
     "bt_glare_params_default", "bt_glare_new", "bt_glare_free", "bt_glare_device", "bt_debug_glare_plane", "bt_debug_glare_host",
+    "bt_resample_params_default", "bt_resample_new", "bt_resample_free", "bt_resample_device", "bt_debug_resample_weights",
+    "bt_debug_resample_plane", "bt_debug_resample_host",
 ]
 
 
@@ -322,6 +335,14 @@ def _load():
     L.bt_glare_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(_CGlareParams), vp]
     L.bt_debug_glare_plane.argtypes = [vp, C.c_uint32, fp, C.c_uint32]
     L.bt_debug_glare_host.argtypes = [fp, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.POINTER(_CGlareParams)]
+    L.bt_resample_params_default.argtypes = [C.POINTER(_CResampleParams)]
+    L.bt_resample_new.restype = vp
+    L.bt_resample_new.argtypes = []
+    L.bt_resample_free.argtypes = [vp]
+    L.bt_resample_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(_CResampleParams), vp]
+    L.bt_debug_resample_weights.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), fp, C.POINTER(C.c_uint32)]
+    L.bt_debug_resample_plane.argtypes = [vp, fp, C.c_uint32]
+    L.bt_debug_resample_host.argtypes = [vp, fp, C.c_uint32, C.c_uint32, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.POINTER(_CResampleParams)]
     return L
 
 
@@ -1200,6 +1221,120 @@ def glare_host(array, samples=1, **params):
     cp = GlareParams(**params)._c()
     _check(lib.bt_debug_glare_host(a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), out.ctypes.data_as(C.POINTER(C.c_float)),
                                    a.shape[1], a.shape[0], C.byref(cp)))
+    return out
+
+
+def _resample_defaults():
+    p = _CResampleParams()
+    lib.bt_resample_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class ResampleParams:
+    """`bt_resample_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_resample_params_default's value; `filter` is a Filter, its name ("lanczos3") or its number."""
+    filter: Optional[int] = None
+    max_value: Optional[float] = None
+    clamp_negative: Optional[int] = None
+
+    def __post_init__(self):
+        d = _resample_defaults()
+        for k, _ in _CResampleParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+        if isinstance(self.filter, str):
+            names = {f.name.lower(): f for f in Filter}
+            if self.filter.lower() not in names:
+                raise BendyError(-1, f"unknown filter {self.filter!r}: one of {', '.join(names)}")
+            self.filter = names[self.filter.lower()]
+
+    def _c(self):
+        return _CResampleParams(int(self.filter), float(self.max_value), int(self.clamp_negative))
+
+
+class Resample:
+    """`bt_resample` (include/bendy_hip.h): EXTENSION, not in the reference -- the resample stage: render at one size, show at
+    another, through a separable filter in scene-linear light, after the glare stage and ahead of the display stage
+    (DESIGN.md 17).  The handle owns the intermediate plane and both weight tables.  Keywords = ResampleParams fields."""
+
+    def __init__(self, **params):
+        self.params = ResampleParams(**params)
+        h = lib.bt_resample_new()
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+        self._plane_dims = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_resample_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _params(self, params):
+        return ResampleParams(**{**{k: getattr(self.params, k) for k, _ in _CResampleParams._fields_}, **params})
+
+    def apply(self, buffer: Buffer, width, height, *, out: Optional[Buffer] = None, **params) -> Buffer:
+        """The frame of `buffer` (running sums of `.samples` samples, or a mean with samples = 1) resampled to width x height ->
+        a Buffer holding the MEAN (samples = 1) with the input's colour space, as `Glare.apply` returns.  Keywords override the
+        handle's ResampleParams for this call."""
+        p = self._params(params)
+        width, height = int(width), int(height)
+        if buffer.device == "cpu":
+            raise BendyError(-1, "apply needs a device-resident buffer (there is no host-buffer variant)")
+        if width < 1 or height < 1:
+            raise BendyError(-1, f"cannot resample to {width}x{height}")
+        import torch
+        if out is None:
+            out = Buffer(width, height, buffer.color_space, device=buffer.device)
+        elif (out.width, out.height) != (width, height) or out.device == "cpu" or out.data.device != buffer.data.device:
+            raise BendyError(-1, f"out must be a {width}x{height} buffer on the input's device")
+        out.color_space = buffer.color_space
+        cp = p._c()
+        _check(lib.bt_resample_device(self._h, buffer.data.data_ptr(), max(buffer.samples, 1), buffer.width, buffer.height,
+                                      out.data.data_ptr(), width, height, C.byref(cp), torch.cuda.current_stream().cuda_stream))
+        self._plane_dims = (width, buffer.height)
+        out.samples = 1
+        return out
+
+    def host(self, array, samples, width, height, **params):
+        """bt_debug_resample_host on this handle (tests, no device): as `resample_host`, and the handle keeps the tables the call
+        used, for `weights`."""
+        return resample_host(array, samples, width, height, _handle=self._h, **{**{k: getattr(self.params, k) for k, _ in _CResampleParams._fields_}, **params})
+
+    def weights(self, axis):
+        """bt_debug_resample_weights (tests): the table of axis 0 / "x" or 1 / "y" of the handle's last call ->
+        (first int32 [dst], T, weights float32 [dst, T], nearest uint32 [dst])."""
+        axis = {"x": 0, "y": 1}.get(axis, axis)
+        sides = (C.c_uint32 * 3)()
+        taps = _check(lib.bt_debug_resample_weights(self._h, int(axis), sides, None, None, None))
+        dst = int(sides[1])
+        first, w, near = np.zeros(dst, dtype=np.int32), np.zeros((dst, taps), dtype=np.float32), np.zeros(dst, dtype=np.uint32)
+        _check(lib.bt_debug_resample_weights(self._h, int(axis), sides, first.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             w.ctypes.data_as(C.POINTER(C.c_float)), near.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return first, taps, w, near
+
+    def plane(self):
+        """bt_debug_resample_plane (tests; synchronises): P of the last `apply` as float32 [h, W, 4]."""
+        n = _check(lib.bt_debug_resample_plane(self._h, None, 0))
+        flat = np.zeros(n, dtype=np.float32)
+        _check(lib.bt_debug_resample_plane(self._h, flat.ctypes.data_as(C.POINTER(C.c_float)), n))
+        w, h = self._plane_dims
+        return flat.reshape(h, w, 4)
+
+
+def resample_host(array, samples, width, height, _handle=None, **params):
+    """bt_debug_resample_host (tests, no device): the whole resample stage on the host through csrc/bt_resample.hpp's own
+    functions.  `array`: float32 [h, w, 4] running sums -> the resampled mean, float32 [height, width, 4]."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise BendyError(-1, "resample_host expects a [H, W, 4] array")
+    out = np.empty((max(int(height), 0), max(int(width), 0), 4), dtype=np.float32)
+    cp = ResampleParams(**params)._c()
+    _check(lib.bt_debug_resample_host(_handle, a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), a.shape[1], a.shape[0],
+                                      out.ctypes.data_as(C.POINTER(C.c_float)), int(width), int(height), C.byref(cp)))
     return out
 
 

@@ -27,6 +27,9 @@
 // --glare STRENGTH [--glare-levels N] [--glare-spread X] (extension too; bt_glare): the mean that is about to be shown (plain,
 // denoised, adaptive-resolved or temporal) passes bt_glare_device first, ahead of bt_display_device or bt_preview_device; under
 // --temporal once per displayed frame.  --hdr then holds the glared mean, because that is what is shown.
+// --resample WxH [--resample-filter box|tent|mitchell|lanczos3] (extension too; bt_resample): the mean that is about to be shown
+// (plain, denoised, adaptive-resolved, temporal, glared) passes bt_resample_device last, ahead of bt_display_device or
+// bt_preview_device; under --temporal once per displayed frame.  The screenshot and --hdr then have W x H pixels.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -118,6 +121,9 @@ struct Args {
     bool glare = false;
     float glare_strength = 0.0f, glare_spread = -1.0f;   // -1: bt_glare_params_default's, as the levels
     long glare_levels = -1;
+    bool resample = false;
+    unsigned resample_width = 0, resample_height = 0;
+    std::string resample_filter;                          // empty: not given (mitchell)
 };
 
 void usage() {
@@ -144,7 +150,11 @@ void usage() {
                  "                             only, not with --shard)\n"
                  "       [--glare STRENGTH] [--glare-levels 6] [--glare-spread 1]   (extension: glare stage -- an energy-conserving bloom\n"
                  "                             on the mean that is shown, ahead of the display stage or the preview; --hdr then holds\n"
-                 "                             the glared mean; --output full only, not with --shard)\n");
+                 "                             the glared mean; --output full only, not with --shard)\n"
+                 "       [--resample WxH] [--resample-filter box|tent|mitchell|lanczos3]   (extension: resample stage -- the mean that is\n"
+                 "                             shown is filtered to W x H last, ahead of the display stage or the preview; the\n"
+                 "                             screenshot and --hdr then have that size; mitchell unless told; --output full only,\n"
+                 "                             not with --shard)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -263,6 +273,19 @@ Args parse(int argc, char **argv) {
             a.glare_levels = std::strtol(spec.c_str(), &end, 10);
             if (spec.empty() || *end != 0 || a.glare_levels < 0 || a.glare_levels > 16) die("--glare-levels expects a count in 0 .. 16");
         }
+        else if (k == "--resample") {
+            const std::string spec = val();
+            char tail = 0;
+            if (std::sscanf(spec.c_str(), "%ux%u%c", &a.resample_width, &a.resample_height, &tail) != 2 || spec[0] < '0' || spec[0] > '9' ||
+                a.resample_width == 0 || a.resample_height == 0 || a.resample_width > 0x7fffffffu || a.resample_height > 0x7fffffffu)
+                die("--resample expects WxH, both positive");
+            a.resample = true;
+        }
+        else if (k == "--resample-filter") {
+            a.resample_filter = val();
+            if (a.resample_filter != "box" && a.resample_filter != "tent" && a.resample_filter != "mitchell" && a.resample_filter != "lanczos3")
+                die("--resample-filter expects box, tent, mitchell or lanczos3");
+        }
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -296,6 +319,9 @@ Args parse(int argc, char **argv) {
     if (!a.glare && (a.glare_levels >= 0 || a.glare_spread > 0.0f)) die("--glare-levels and --glare-spread need --glare");
     if (a.glare && a.output != "full") die("--glare needs --output full");
     if (a.glare && a.shard_world > 1) die("--glare does not apply to a --shard run");
+    if (!a.resample && !a.resample_filter.empty()) die("--resample-filter needs --resample");
+    if (a.resample && a.output != "full") die("--resample needs --output full");
+    if (a.resample && a.shard_world > 1) die("--resample does not apply to a --shard run");
     return a;
 }
 
@@ -357,7 +383,8 @@ int main(int argc, char **argv) {
     float *d_frame = nullptr;
     uint8_t *d_rgba8 = nullptr;
     hip_check(hipMalloc((void **)&d_frame, n_px * 16), "hipMalloc");
-    hip_check(hipMalloc((void **)&d_rgba8, n_px * 4), "hipMalloc");
+    const size_t n_shown = args.resample ? (size_t)args.resample_width * args.resample_height : n_px;     // the frame that is shown
+    hip_check(hipMalloc((void **)&d_rgba8, n_shown * 4), "hipMalloc");
     hip_check(hipMemcpy(d_frame, init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
 
     // --denoise-inline (extension): the guides' frames and the denoised mean; every call below fills all four in one pass
@@ -447,6 +474,20 @@ int main(int argc, char **argv) {
                       glare_levels, gp.spread);
         glare_json = gj;
     }
+    // --resample (extension): the mean that is shown is filtered to another size last
+    bt_resample *resample = nullptr;
+    bt_resample_params rp;
+    bt_resample_params_default(&rp);
+    float *d_resampled = nullptr;                          // the resampled mean
+    const unsigned shown_w = args.resample ? args.resample_width : args.width, shown_h = args.resample ? args.resample_height : args.height;
+    if (args.resample) {
+        resample = bt_resample_new();
+        if (!resample) die(bt_last_error());
+        if (!args.resample_filter.empty())
+            rp.filter = args.resample_filter == "box" ? BT_RESAMPLE_BOX : args.resample_filter == "tent" ? BT_RESAMPLE_TENT
+                      : args.resample_filter == "mitchell" ? BT_RESAMPLE_MITCHELL : BT_RESAMPLE_LANCZOS3;
+        hip_check(hipMalloc((void **)&d_resampled, n_shown * 16), "hipMalloc");
+    }
     // --temporal (extension): one guided render into cleared frames and one accumulate per displayed frame
     bt_temporal *temporal = nullptr;
     double history_mean = 0.0, history_min = 0.0;
@@ -472,11 +513,17 @@ int main(int argc, char **argv) {
             check(bt_temporal_accumulate_device(temporal, &view, d_frame, args.samples * nn, d_guides[1], args.samples * nn, d_guides[2],
                                                 args.samples * nn, d_mean, nullptr, nullptr),
                   "bt_temporal_accumulate_device");
-            // every displayed frame passes the glare and the display stage; the last one does below, on the frame the screenshot shows
+            // every displayed frame passes the glare, the resample and the display stage; the last one does below, on the frame the
+            // screenshot shows
             if (glare && f + 1 < args.frames)
                 check(bt_glare_device(glare, d_mean, 1, d_glare, args.width, args.height, &gp, nullptr), "bt_glare_device");
+            if (resample && f + 1 < args.frames)
+                check(bt_resample_device(resample, glare ? d_glare : d_mean, 1, args.width, args.height, d_resampled, shown_w, shown_h, &rp,
+                                         nullptr),
+                      "bt_resample_device");
             if (display && f + 1 < args.frames)
-                check(bt_display_device(display, glare ? d_glare : d_mean, 1, d_rgba8, args.width, args.height, color_space, &dp, nullptr),
+                check(bt_display_device(display, resample ? d_resampled : glare ? d_glare : d_mean, 1, d_rgba8, shown_w, shown_h, color_space,
+                                        &dp, nullptr),
                       "bt_display_device");
             hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
             const double delta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -547,6 +594,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "%.1f Msamples/s (render calls only)\n",
                  sum_delta > 0 ? (double)n_px * buffer_samples / sum_delta / 1e6 : 0.0);
 
+    std::string resample_json;                             // filled once the frame has been resampled
     auto write_stats = [&](const char *display_json) {
         FILE *f = std::fopen(args.stats_json.c_str(), "w");
         if (!f) die("cannot write " + args.stats_json);
@@ -558,10 +606,11 @@ int main(int argc, char **argv) {
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
         std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, glare_json.c_str(), display_json);
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (glare_json + resample_json).c_str(), display_json);
         std::fclose(f);
     };
-    if (!args.stats_json.empty() && !display) write_stats("");        // with the display stage: once the frame has been shown
+    // with the display or the resample stage: once the frame has been shown
+    if (!args.stats_json.empty() && !display && !resample) write_stats("");
 
     // Ctrl+P (main.rs:275-298)
     std::string shot = args.screenshot;
@@ -660,8 +709,26 @@ int main(int argc, char **argv) {
         shown_samples = 1;                                  // the glared buffer holds a mean
         std::fprintf(stderr, "glare: strength %g over %u levels, spread %g\n", gp.strength, glare_levels, gp.spread);
     }
+    if (resample) {
+        check(bt_resample_device(resample, d_shown, shown_samples, args.width, args.height, d_resampled, shown_w, shown_h, &rp, nullptr),
+              "bt_resample_device");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        d_shown = d_resampled;
+        shown_samples = 1;                                  // the resampled buffer holds a mean
+        const int taps_x = bt_debug_resample_weights(resample, 0, nullptr, nullptr, nullptr, nullptr);
+        const int taps_y = bt_debug_resample_weights(resample, 1, nullptr, nullptr, nullptr, nullptr);
+        check(std::min(taps_x, taps_y), "bt_debug_resample_weights");
+        const char *names[4] = {"box", "tent", "mitchell", "lanczos3"};
+        std::fprintf(stderr, "resample: %ux%u -> %ux%u, %s, %d x %d taps\n", args.width, args.height, shown_w, shown_h, names[rp.filter], taps_x,
+                     taps_y);
+        char rj[192];
+        std::snprintf(rj, sizeof rj, ", \"resample\": {\"width\": %u, \"height\": %u, \"filter\": \"%s\", \"taps_x\": %d, \"taps_y\": %d}", shown_w,
+                      shown_h, names[rp.filter], taps_x, taps_y);
+        resample_json = rj;
+        if (!args.stats_json.empty() && !display) write_stats("");
+    }
     if (display) {
-        check(bt_display_device(display, d_shown, shown_samples, d_rgba8, args.width, args.height, color_space, &dp, nullptr), "bt_display_device");
+        check(bt_display_device(display, d_shown, shown_samples, d_rgba8, shown_w, shown_h, color_space, &dp, nullptr), "bt_display_device");
         float ev = 0.0f, mult = 0.0f;
         uint32_t counters[258];
         check(bt_display_exposure(display, &ev, &mult), "bt_display_exposure");
@@ -676,18 +743,18 @@ int main(int argc, char **argv) {
         }
     }
     if (!args.hdr.empty()) {
-        std::vector<float> lin(n_px * 4);
-        hip_check(hipMemcpy(lin.data(), d_shown, n_px * 16, hipMemcpyDeviceToHost), "hipMemcpy");
-        check(bt_write_pfm(args.hdr.c_str(), lin.data(), args.width, args.height, shown_samples), "bt_write_pfm");
+        std::vector<float> lin(n_shown * 4);
+        hip_check(hipMemcpy(lin.data(), d_shown, n_shown * 16, hipMemcpyDeviceToHost), "hipMemcpy");
+        check(bt_write_pfm(args.hdr.c_str(), lin.data(), shown_w, shown_h, shown_samples), "bt_write_pfm");
         std::fprintf(stderr, "saved linear frame to %s\n", args.hdr.c_str());
     }
     if (!args.no_screenshot) {
         if (!display)
-            check(bt_preview_device(d_shown, d_rgba8, args.width, args.height, shown_samples, color_space, nullptr),
+            check(bt_preview_device(d_shown, d_rgba8, shown_w, shown_h, shown_samples, color_space, nullptr),
                   "bt_preview_device");
-        std::vector<uint8_t> rgba8(n_px * 4);
-        hip_check(hipMemcpy(rgba8.data(), d_rgba8, n_px * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-        check(bt_write_png(shot.c_str(), rgba8.data(), args.width, args.height), "bt_write_png");
+        std::vector<uint8_t> rgba8(n_shown * 4);
+        hip_check(hipMemcpy(rgba8.data(), d_rgba8, n_shown * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        check(bt_write_png(shot.c_str(), rgba8.data(), shown_w, shown_h), "bt_write_png");
         std::fprintf(stderr, "saved screenshot to %s\n", shot.c_str());
     }
 
@@ -705,6 +772,8 @@ int main(int argc, char **argv) {
     bt_display_free(display);
     bt_glare_free(glare);
     if (d_glare) (void)hipFree(d_glare);
+    bt_resample_free(resample);
+    if (d_resampled) (void)hipFree(d_resampled);
     for (float *g : d_guides)
         if (g) (void)hipFree(g);
     bt_scene_free(scene);

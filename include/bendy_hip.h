@@ -565,6 +565,68 @@ int bt_debug_glare_plane(bt_glare *g, uint32_t level, float *host, uint32_t n);
 int bt_debug_glare_host(const float *rgba_host, uint32_t samples, float *out_host, uint32_t width, uint32_t height,
                         const bt_glare_params *params);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: resample stage -- render at one size, show at another -------------------
+ * A separable filter from a frame of w x h RGBA32F running sums with its sample count n (a mean is n = 1) to a MEAN of W x H, any
+ * W, H >= 1, each axis larger, smaller or equal on its own.  It sits after the glare stage and before the display stage, in
+ * scene-linear light, so exposure is metered on what is shown.  The reference's viewer resizes its buffer to the window
+ * (main.rs:338-342) and has no such filter: this stage is off unless called, makes no parity claim and changes neither a render
+ * nor bt_preview*, bt_display_*, bt_glare_*, bt_denoise* or bt_temporal_*.  Pixels are float32 in the order written, without
+ * fused multiply-adds; the weight tables are float64 on the host (csrc/bt_resample.hpp has the same lines as code;
+ * tests/resample_ref.py in numpy):
+ *   1. sanitise: the glare stage's step 1, the same function -- r = 1 / n; c = rgb * r; NaN and negatives -> 0; capped at
+ *      max_value.  It precedes every tap: a NaN does not spread over a filter footprint.
+ *   2. tables, per axis (src -> dst texels), built once per (src, dst, filter) and kept on the handle:  ratio = (double)src / dst;
+ *      s = max(1, ratio);  c_i = (i + 0.5) * ratio - 0.5;  taps j = ceil(c_i - R s) .. floor(c_i + R s) with R = 0.5, 1, 2, 3 for
+ *      box, tent, mitchell, lanczos3;  k_j = k((j - c_i) / s);  S = their sum in ascending j;  w_ij = (float)(k_j / S).  T is the
+ *      axis's largest tap count; shorter rows are padded with weights 0.  nearest_i = min(src - 1, floor((i + 0.5) * ratio)).
+ *      k: box 1 on [-0.5, 0.5); tent 1 - |x|; mitchell the B = C = 1/3 cubic as (((21a - 36)a)a + 16) / 18 for a = |x| < 1 and
+ *      (((-7a + 36)a - 60)a + 32) / 18 for 1 <= a < 2; lanczos3 (sin(p) / p) * (sin(q) / q) with p = pi x, q = p / 3, exactly 1 at
+ *      0 and exactly 0 at every other x == rint(x); every k is 0 outside its support.
+ *   3. horizontal: P(i, y) = sum over the T_x taps of w * s(clamp(j, 0, w - 1), y), as acc = 0; acc = acc + w * v in ascending j,
+ *      the product rounded, then the sum; a tap clamped to the border keeps its own weight (edge replication).  P is W x h.
+ *   4. vertical: the same over P with the y table -> W x H.
+ *   5. clamp_negative: out = acc >= 0 ? acc : 0 (mitchell and lanczos3 have negative lobes and undershoot next to an emitter).
+ *   6. out.a = the input's a at (nearest_x, nearest_y): not filtered, not divided by n.
+ * At W x H = w x h tent and lanczos3 return the sanitised mean bit for bit; box at w = 2 W has the weights 0.5, 0.5. */
+typedef enum { BT_RESAMPLE_BOX = 0, BT_RESAMPLE_TENT = 1, BT_RESAMPLE_MITCHELL = 2, BT_RESAMPLE_LANCZOS3 = 3 } bt_resample_filter;
+typedef struct {
+    int32_t filter;            /* a bt_resample_filter */
+    float max_value;           /* > 0, finite: the cap of step 1 */
+    int32_t clamp_negative;    /* step 5: 0 keeps the undershoot */
+} bt_resample_params;
+typedef struct bt_resample bt_resample;   /* owns P (16 B per texel of W x h) and both tables, host and device; one stream at a time */
+/* mitchell, max_value 65536 (the glare stage's cap), clamp_negative 1. */
+void bt_resample_params_default(bt_resample_params *out);
+/* No device work happens here: the handle allocates on its first bt_resample_device, on the device current then, and grows on
+ * demand. */
+bt_resample *bt_resample_new(void);
+void bt_resample_free(bt_resample *h);
+/* Two kernels on `stream`, one per pass, after the uploads of a table that changed (on `stream` too); returns without
+ * synchronising, except that a call which replaces a table first waits for the handle's previous call, whose upload may still
+ * read it.  `rgba_device`: width * height RGBA32F running sums of `samples` samples; `out_device`: out_width * out_height
+ * RGBA32F, the mean.  params == NULL: the defaults.  Checked before the device is touched, in this order, all
+ * BT_ERR_INVALID_ARG: NULL handle, input or output; samples == 0; a zero side, a side of 2^31 and more or 2^32 pixels and more,
+ * on either frame; output equal to input; a filter that is no bt_resample_filter; max_value not finite or <= 0; T > 128 on the
+ * x axis, then on the y axis (lanczos3 beyond about 21 : 1, mitchell 32 : 1, tent 64 : 1, box 127 : 1; the message names the axis
+ * and the ratio).  A valid call without a device returns BT_ERR_DEVICE, and so does a plane whose 32 x 8 tiles do not fit one
+ * launch (2^24 tiles and more).
+ * Not provided: host buffers, sharded frames, edge-aware or guide-driven upsampling, resampling of the albedo / normal / depth
+ * outputs (step 1 would clamp them), any change to the size the render kernels work at. */
+int bt_resample_device(bt_resample *h, const float *rgba_device, uint32_t samples, uint32_t width, uint32_t height, float *out_device,
+                       uint32_t out_width, uint32_t out_height, const bt_resample_params *params, void *stream);
+/* For tests: the table of axis 0 (x) or 1 (y) that the handle's last call -- bt_resample_device or bt_debug_resample_host --
+ * built or reused.  Returns T.  Any pointer may be NULL; `sides` receives {src, dst, filter}, `first` the dst first taps
+ * (unclamped: first_i + t is clamped where it is used), `weights` dst rows of T, `nearest` the dst nearest source indices.
+ * BT_ERR_INVALID_ARG while there is no table. */
+int bt_debug_resample_weights(bt_resample *h, int axis, uint32_t *sides, int32_t *first, float *weights, uint32_t *nearest);
+/* For tests: P of the last bt_resample_device as RGBA float, out_width x height, the fourth channel 0.  n == 0 returns the element
+ * count, else up to n floats are copied to `host` (synchronises) and the number copied is returned. */
+int bt_debug_resample_plane(bt_resample *h, float *host, uint32_t n);
+/* For tests, no device: the whole definition on the host through csrc/bt_resample.hpp's own functions.  The same checks as
+ * bt_resample_device; `h` may be NULL, else the tables are the handle's (kept for bt_debug_resample_weights). */
+int bt_debug_resample_host(bt_resample *h, const float *rgba_host, uint32_t samples, uint32_t width, uint32_t height, float *out_host,
+                           uint32_t out_width, uint32_t out_height, const bt_resample_params *params);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);

@@ -170,4 +170,24 @@ class Glare {
     bt_glare *h_;
 };
 
+// EXTENSION, not in the reference: a thin delegate of the resample stage (bt_resample in bendy_hip.h) -- render at
+// one size, show at another: a separable filter on device-resident frames, after Glare and ahead of bt_display_device or
+// bt_preview_device.  `out` receives a MEAN of out_width x out_height: preview or display it with samples = 1.
+class Resample {
+  public:
+    bt_resample_params params;
+    Resample() : h_(bt_resample_new()) { if (!h_) throw Error(bt_last_error_code(), bt_last_error()); bt_resample_params_default(&params); }
+    Resample(const Resample &) = delete;
+    Resample &operator=(const Resample &) = delete;
+    ~Resample() { bt_resample_free(h_); }
+    void apply(const float *rgba_device, unsigned samples, unsigned width, unsigned height, float *out_device, unsigned out_width,
+               unsigned out_height, void *stream = nullptr) {
+        check(bt_resample_device(h_, rgba_device, samples, width, height, out_device, out_width, out_height, &params, stream));
+    }
+    bt_resample *handle() const { return h_; }
+
+  private:
+    bt_resample *h_;
+};
+
 } // namespace bendy
