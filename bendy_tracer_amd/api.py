@@ -187,6 +187,14 @@ class _CResampleParams(C.Structure):  # include/bendy_hip.h `bt_resample_params`
     _fields_ = [("filter", C.c_int32), ("max_value", C.c_float), ("clamp_negative", C.c_int32)]
 
 
+class _CDespeckleParams(C.Structure):  # include/bendy_hip.h `bt_despeckle_params` (extension)
+    _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("ratio", C.c_float), ("floor", C.c_float), ("max_value", C.c_float)]
+
+
+class DespeckleStats(C.Structure):  # include/bendy_hip.h `bt_despeckle_stats` (extension)
+    _fields_ = [("flagged", C.c_uint32), ("sanitised", C.c_uint32), ("pixels", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -213,6 +221,8 @@ EXPORTS = [
     "bt_glare_params_default", "bt_glare_new", "bt_glare_free", "bt_glare_device", "bt_debug_glare_plane", "bt_debug_glare_host",
     "bt_resample_params_default", "bt_resample_new", "bt_resample_free", "bt_resample_device", "bt_debug_resample_weights",
     "bt_debug_resample_plane", "bt_debug_resample_host",
+    "bt_despeckle_params_default", "bt_despeckle_new", "bt_despeckle_free", "bt_despeckle_device", "bt_despeckle_poll",
+    "bt_debug_despeckle_host",
 ]
 
 
@@ -343,6 +353,13 @@ def _load():
     L.bt_debug_resample_weights.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), fp, C.POINTER(C.c_uint32)]
     L.bt_debug_resample_plane.argtypes = [vp, fp, C.c_uint32]
     L.bt_debug_resample_host.argtypes = [vp, fp, C.c_uint32, C.c_uint32, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.POINTER(_CResampleParams)]
+    L.bt_despeckle_params_default.argtypes = [C.POINTER(_CDespeckleParams)]
+    L.bt_despeckle_new.restype = vp
+    L.bt_despeckle_new.argtypes = []
+    L.bt_despeckle_free.argtypes = [vp]
+    L.bt_despeckle_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(_CDespeckleParams), vp]
+    L.bt_despeckle_poll.argtypes = [vp, C.POINTER(DespeckleStats)]
+    L.bt_debug_despeckle_host.argtypes = [fp, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.POINTER(_CDespeckleParams), C.POINTER(DespeckleStats)]
     return L
 
 
@@ -1336,6 +1353,94 @@ def resample_host(array, samples, width, height, _handle=None, **params):
     _check(lib.bt_debug_resample_host(_handle, a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), a.shape[1], a.shape[0],
                                       out.ctypes.data_as(C.POINTER(C.c_float)), int(width), int(height), C.byref(cp)))
     return out
+
+
+def _despeckle_defaults():
+    p = _CDespeckleParams()
+    lib.bt_despeckle_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class DespeckleParams:
+    """`bt_despeckle_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_despeckle_params_default's value."""
+    radius: Optional[int] = None
+    rank: Optional[int] = None
+    ratio: Optional[float] = None
+    floor: Optional[float] = None
+    max_value: Optional[float] = None
+
+    def __post_init__(self):
+        d = _despeckle_defaults()
+        for k, _ in _CDespeckleParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+
+    def _c(self):
+        return _CDespeckleParams(int(self.radius), int(self.rank), float(self.ratio), float(self.floor), float(self.max_value))
+
+
+class Despeckle:
+    """`bt_despeckle` (include/bendy_hip.h): EXTENSION, not in the reference -- the despeckle stage: rank-order firefly rejection
+    on a frame of running sums, ahead of every other stage.  The handle owns two counters on the device.
+    Keywords = DespeckleParams fields."""
+
+    def __init__(self, **params):
+        self.params = DespeckleParams(**params)
+        h = lib.bt_despeckle_new()
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_despeckle_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def apply(self, buffer: Buffer, *, out: Optional[Buffer] = None, **params) -> Buffer:
+        """The frame of `buffer` (running sums of `.samples` samples, or a mean with samples = 1) with its outliers pulled down
+        -> a Buffer of SUMS of the same `.samples`, with the input's colour space: it takes the input's place anywhere in the
+        chain.  Keywords override the handle's DespeckleParams for this call."""
+        p = DespeckleParams(**{**{k: getattr(self.params, k) for k, _ in _CDespeckleParams._fields_}, **params})
+        if buffer.device == "cpu":
+            raise BendyError(-1, "apply needs a device-resident buffer (there is no host-buffer variant)")
+        import torch
+        if out is None:
+            out = Buffer(buffer.width, buffer.height, buffer.color_space, device=buffer.device)
+        elif out is buffer:
+            raise BendyError(-1, "out must not be the input: every neighbour value is the input's")
+        elif (out.width, out.height) != (buffer.width, buffer.height) or out.device == "cpu" or out.data.device != buffer.data.device:
+            raise BendyError(-1, f"out must be a {buffer.width}x{buffer.height} buffer on the input's device")
+        out.color_space = buffer.color_space
+        cp = p._c()
+        _check(lib.bt_despeckle_device(self._h, buffer.data.data_ptr(), max(buffer.samples, 1), out.data.data_ptr(), buffer.width,
+                                       buffer.height, C.byref(cp), torch.cuda.current_stream().cuda_stream))
+        out.samples = buffer.samples
+        return out
+
+    def poll(self) -> DespeckleStats:
+        """bt_despeckle_poll (synchronises): the last `apply`'s DespeckleStats -- flagged, sanitised, pixels."""
+        st = DespeckleStats()
+        _check(lib.bt_despeckle_poll(self._h, C.byref(st)))
+        return st
+
+
+def despeckle_host(array, samples=1, stats=False, **params):
+    """bt_debug_despeckle_host (tests, no device): the whole despeckle stage on the host through csrc/bt_despeckle.hpp's own
+    functions.  `array`: float32 [H, W, 4] running sums -> the despeckled sums, float32 [H, W, 4]; with stats=True also the
+    DespeckleStats."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise BendyError(-1, "despeckle_host expects a [H, W, 4] array")
+    out = np.empty_like(a)
+    cp = DespeckleParams(**params)._c()
+    st = DespeckleStats()
+    _check(lib.bt_debug_despeckle_host(a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                       a.shape[1], a.shape[0], C.byref(cp), C.byref(st)))
+    return (out, st) if stats else out
 
 
 _default_denoiser = None

@@ -30,6 +30,9 @@
 // --resample WxH [--resample-filter box|tent|mitchell|lanczos3] (extension too; bt_resample): the mean that is about to be shown
 // (plain, denoised, adaptive-resolved, temporal, glared) passes bt_resample_device last, ahead of bt_display_device or
 // bt_preview_device; under --temporal once per displayed frame.  The screenshot and --hdr then have W x H pixels.
+// --despeckle RATIO [--despeckle-rank K] [--despeckle-radius R] (extension too; bt_despeckle): the colour sums pass
+// bt_despeckle_device right after the render and before everything else -- under --temporal each frame's sums before the
+// accumulate, with --adaptive the resolved mean (n = 1), because tiles hold different counts.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -124,6 +127,9 @@ struct Args {
     bool resample = false;
     unsigned resample_width = 0, resample_height = 0;
     std::string resample_filter;                          // empty: not given (mitchell)
+    bool despeckle = false;
+    float despeckle_ratio = 0.0f;
+    long despeckle_rank = -1, despeckle_radius = -1;      // -1: bt_despeckle_params_default's
 };
 
 void usage() {
@@ -154,6 +160,10 @@ void usage() {
                  "       [--resample WxH] [--resample-filter box|tent|mitchell|lanczos3]   (extension: resample stage -- the mean that is\n"
                  "                             shown is filtered to W x H last, ahead of the display stage or the preview; the\n"
                  "                             screenshot and --hdr then have that size; mitchell unless told; --output full only,\n"
+                 "                             not with --shard)\n"
+                 "       [--despeckle RATIO] [--despeckle-rank 2] [--despeckle-radius 1]   (extension: despeckle stage -- a pixel brighter\n"
+                 "                             than RATIO times the rank-th brightest of its neighbours is pulled down to that, on the\n"
+                 "                             colour sums right after the render and before every other stage; --output full only,\n"
                  "                             not with --shard)\n");
 }
 
@@ -286,6 +296,27 @@ Args parse(int argc, char **argv) {
             if (a.resample_filter != "box" && a.resample_filter != "tent" && a.resample_filter != "mitchell" && a.resample_filter != "lanczos3")
                 die("--resample-filter expects box, tent, mitchell or lanczos3");
         }
+        else if (k == "--despeckle") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.despeckle_ratio = std::strtof(spec.c_str(), &end);
+            if (spec.empty() || *end != 0 || !(a.despeckle_ratio >= 1.0f) || !(a.despeckle_ratio < 3.0e38f))
+                die("--despeckle expects a finite ratio >= 1");
+            a.despeckle = true;
+        }
+        else if (k == "--despeckle-rank" || k == "--despeckle-radius") {
+            const std::string spec = val();
+            char *end = nullptr;
+            const long n = std::strtol(spec.c_str(), &end, 10);
+            const bool ok = !spec.empty() && *end == 0;
+            if (k == "--despeckle-rank") {
+                if (!ok || n < 1 || n > 24) die("--despeckle-rank expects a count in 1 .. 24");
+                a.despeckle_rank = n;
+            } else {
+                if (!ok || (n != 1 && n != 2)) die("--despeckle-radius expects 1 or 2");
+                a.despeckle_radius = n;
+            }
+        }
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -322,6 +353,11 @@ Args parse(int argc, char **argv) {
     if (!a.resample && !a.resample_filter.empty()) die("--resample-filter needs --resample");
     if (a.resample && a.output != "full") die("--resample needs --output full");
     if (a.resample && a.shard_world > 1) die("--resample does not apply to a --shard run");
+    if (!a.despeckle && (a.despeckle_rank >= 0 || a.despeckle_radius >= 0)) die("--despeckle-rank and --despeckle-radius need --despeckle");
+    if (a.despeckle && a.output != "full") die("--despeckle needs --output full");
+    if (a.despeckle && a.shard_world > 1) die("--despeckle does not apply to a --shard run");
+    if (a.despeckle && a.despeckle_rank > (a.despeckle_radius == 2 ? 24 : 8))
+        die("--despeckle-rank must not exceed the window's neighbours: 8 at radius 1, 24 at --despeckle-radius 2");
     return a;
 }
 
@@ -488,6 +524,20 @@ int main(int argc, char **argv) {
                       : args.resample_filter == "mitchell" ? BT_RESAMPLE_MITCHELL : BT_RESAMPLE_LANCZOS3;
         hip_check(hipMalloc((void **)&d_resampled, n_shown * 16), "hipMalloc");
     }
+    // --despeckle (extension): the colour sums pass the despeckle stage right after the render, before everything else
+    bt_despeckle *despeckle = nullptr;
+    bt_despeckle_params sp;
+    bt_despeckle_params_default(&sp);
+    bt_despeckle_stats sstats{};                           // of the last call
+    float *d_despeckled = nullptr;                         // the despeckled sums
+    if (args.despeckle) {
+        despeckle = bt_despeckle_new();
+        if (!despeckle) die(bt_last_error());
+        sp.ratio = args.despeckle_ratio;
+        if (args.despeckle_rank >= 0) sp.rank = (uint32_t)args.despeckle_rank;
+        if (args.despeckle_radius >= 0) sp.radius = (uint32_t)args.despeckle_radius;
+        hip_check(hipMalloc((void **)&d_despeckled, n_px * 16), "hipMalloc");
+    }
     // --temporal (extension): one guided render into cleared frames and one accumulate per displayed frame
     bt_temporal *temporal = nullptr;
     double history_mean = 0.0, history_min = 0.0;
@@ -510,7 +560,10 @@ int main(int argc, char **argv) {
             check(bt_render_guided_device(scene, camera, &cfg, &rc, d_frame, d_guides[0], d_guides[1], d_guides[2], args.width,
                                           args.height, args.seed, nullptr),
                   "bt_render_guided_device");
-            check(bt_temporal_accumulate_device(temporal, &view, d_frame, args.samples * nn, d_guides[1], args.samples * nn, d_guides[2],
+            if (despeckle)                                  // this frame's sums, before they enter the history
+                check(bt_despeckle_device(despeckle, d_frame, args.samples * nn, d_despeckled, args.width, args.height, &sp, nullptr),
+                      "bt_despeckle_device");
+            check(bt_temporal_accumulate_device(temporal, &view, despeckle ? d_despeckled : d_frame, args.samples * nn, d_guides[1], args.samples * nn, d_guides[2],
                                                 args.samples * nn, d_mean, nullptr, nullptr),
                   "bt_temporal_accumulate_device");
             // every displayed frame passes the glare, the resample and the display stage; the last one does below, on the frame the
@@ -594,6 +647,24 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "%.1f Msamples/s (render calls only)\n",
                  sum_delta > 0 ? (double)n_px * buffer_samples / sum_delta / 1e6 : 0.0);
 
+    std::string despeckle_json;
+    if (despeckle) {
+        // the resolved mean of --adaptive (n = 1: tiles hold different counts), else the sums of the whole render; under --temporal
+        // every frame has passed already and the counts are the last frame's
+        if (args.adaptive)
+            check(bt_despeckle_device(despeckle, d_mean, 1, d_despeckled, args.width, args.height, &sp, nullptr), "bt_despeckle_device");
+        else if (!args.temporal)
+            check(bt_despeckle_device(despeckle, d_frame, buffer_samples ? buffer_samples : 1, d_despeckled, args.width, args.height, &sp,
+                                      nullptr),
+                  "bt_despeckle_device");
+        check(bt_despeckle_poll(despeckle, &sstats), "bt_despeckle_poll");
+        std::fprintf(stderr, "despeckle: ratio %g, rank %u, radius %u: %u of %u pixels pulled down, %u sanitised\n", sp.ratio, sp.rank, sp.radius,
+                     sstats.flagged, sstats.pixels, sstats.sanitised);
+        char sj[200];
+        std::snprintf(sj, sizeof sj, ", \"despeckle\": {\"ratio\": %.9g, \"rank\": %u, \"radius\": %u, \"flagged\": %u, \"sanitised\": %u}", sp.ratio,
+                      sp.rank, sp.radius, sstats.flagged, sstats.sanitised);
+        despeckle_json = sj;
+    }
     std::string resample_json;                             // filled once the frame has been resampled
     auto write_stats = [&](const char *display_json) {
         FILE *f = std::fopen(args.stats_json.c_str(), "w");
@@ -606,7 +677,7 @@ int main(int argc, char **argv) {
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
         std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (glare_json + resample_json).c_str(), display_json);
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (despeckle_json + glare_json + resample_json).c_str(), display_json);
         std::fclose(f);
     };
     // with the display or the resample stage: once the frame has been shown
@@ -630,14 +701,14 @@ int main(int argc, char **argv) {
         }
     }
     // --denoise (extension): the guides of the same frame into fresh buffers, then the screenshot shows the denoised mean
-    float *d_shown = d_frame;
+    float *d_shown = despeckle && !args.temporal ? d_despeckled : d_frame;
     unsigned shown_samples = buffer_samples ? buffer_samples : 1;
     if (args.temporal) {                                    // everything below sees the accumulated mean
         d_shown = d_mean;
         shown_samples = 1;
     }
     if (args.adaptive) {                                    // everything below sees the resolved mean
-        d_shown = d_mean;
+        d_shown = despeckle ? d_despeckled : d_mean;
         shown_samples = 1;
         if (!args.adaptive_map.empty()) {
             // the per-tile counts as a grey image, one pixel per tile, 255 = the cap
@@ -656,7 +727,7 @@ int main(int argc, char **argv) {
     }
     if (args.denoise_inline && !args.no_screenshot) {
         bt_denoiser *dn = bt_denoiser_new();
-        check(bt_denoise_device(dn, d_frame, shown_samples, d_guides[0], shown_samples, d_guides[1], shown_samples, d_guides[2],
+        check(bt_denoise_device(dn, d_shown, shown_samples, d_guides[0], shown_samples, d_guides[1], shown_samples, d_guides[2],
                                 shown_samples, d_guides[3], args.width, args.height, nullptr, nullptr),
               "bt_denoise_device");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
@@ -770,6 +841,8 @@ int main(int argc, char **argv) {
     bt_adaptive_free(adaptive);
     bt_temporal_free(temporal);
     bt_display_free(display);
+    bt_despeckle_free(despeckle);
+    if (d_despeckled) (void)hipFree(d_despeckled);
     bt_glare_free(glare);
     if (d_glare) (void)hipFree(d_glare);
     bt_resample_free(resample);

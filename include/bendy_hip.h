@@ -627,6 +627,69 @@ int bt_debug_resample_plane(bt_resample *h, float *host, uint32_t n);
 int bt_debug_resample_host(bt_resample *h, const float *rgba_host, uint32_t samples, uint32_t width, uint32_t height, float *out_host,
                            uint32_t out_width, uint32_t out_height, const bt_resample_params *params);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: despeckle stage -- rank-order firefly rejection ahead of the chain -------
+ * A path tracer at low sample counts leaves single pixels far brighter than anything around them, and every later stage makes
+ * them worse: the denoiser's colour stop keeps them as edges, the temporal history takes many frames to forget them, the glare
+ * stage turns each into a halo and a filter with negative lobes rings around it.  This stage pulls a pixel whose luminance
+ * exceeds `ratio` times the `rank`-th brightest of its neighbours down to that limit.  It is off unless called, makes no parity
+ * claim and changes neither a render nor any other stage.  The input is a frame of RGBA32F running sums with its sample count n
+ * (a mean is n = 1); the output is in the input's units -- SUMS of the same n, not a mean -- so the stage can stand in front of
+ * bt_temporal_accumulate_device without falsifying its history lengths, and anywhere else in the chain.  Everything is float32
+ * in the order written, without fused multiply-adds, with correctly rounded `/` (csrc/bt_despeckle.hpp has the same lines as
+ * code; tests/despeckle_ref.py in numpy):
+ *   1. on the host:  fn = (float)n;  cap = max_value * fn;  fl = floor * fn.
+ *   2. sanitise, per pixel and channel of rgb:  s = v >= 0 ? v : 0 (NaN and negatives -> 0);  s = s < cap ? s : cap;
+ *      Y = (0.2126 * s.x + 0.7152 * s.y) + 0.0722 * s.z, the display meter's luminance.
+ *   3. the neighbours of pixel (x, y) are the in-frame pixels of the (2 radius + 1)^2 window, centre excluded.  Out-of-frame taps
+ *      are absent, not clamped (with replicated borders a corner pixel would be three of its own eight neighbours and could
+ *      never be flagged):  M = (min(x + R, W - 1) - max(x - R, 0) + 1) * (min(y + R, H - 1) - max(y - R, 0) + 1) - 1;
+ *      k = min(rank, M);  a pixel with M = 0 is never flagged.
+ *   4. T = the k-th largest neighbour Y (1 = the brightest): an order statistic of non-negative finite floats, whose value does
+ *      not depend on how it is selected.
+ *   5. lim = T * ratio + fl.
+ *   6. Y > lim: the pixel is flagged, g = lim / Y, out.rgb = s * g.  Otherwise out.rgb = s.  In both cases out.a = the input's a.
+ * Every neighbour value is the input's: the stage is single pass and order-free.  A clean, unflagged pixel comes back bit for
+ * bit, -0.0 included.  A bright feature survives where every pixel of it has at least `rank` neighbours as bright as itself,
+ * within `ratio`: at radius 1, rank 2 isolated pixels and adjacent pairs are pulled down, 2 x 2 blocks, L-shaped triples and the
+ * interior of a one-pixel line are kept -- and the two end pixels of such a line are not. */
+typedef struct {
+    uint32_t radius;           /* 1 or 2: the window is (2 radius + 1)^2 */
+    uint32_t rank;             /* 1 .. (2 radius + 1)^2 - 1 */
+    float ratio;               /* >= 1, finite */
+    float floor;               /* >= 0, finite: in units of the mean, so that a pixel in a black neighbourhood is judged against it */
+    float max_value;           /* > 0, finite: the cap of step 2, in units of the mean */
+} bt_despeckle_params;
+typedef struct {
+    uint32_t flagged;          /* pixels step 6 pulled down */
+    uint32_t sanitised;        /* pixels in which step 2 changed a channel */
+    uint32_t pixels;           /* width * height of the call */
+    uint32_t reserved;
+} bt_despeckle_stats;
+typedef struct bt_despeckle bt_despeckle;   /* owns two uint32 counters on the device; one stream at a time */
+/* radius 1, rank 2, ratio 4, floor 0.01, max_value 65536 (the glare stage's cap).  Starting values; DESIGN.md 18 has the sweep. */
+void bt_despeckle_params_default(bt_despeckle_params *out);
+/* No device work happens here: the handle allocates its counters on its first bt_despeckle_device, on the device current then. */
+bt_despeckle *bt_despeckle_new(void);
+void bt_despeckle_free(bt_despeckle *h);
+/* One kernel on `stream`, after the counters have been zeroed on it; returns without synchronising.  `rgba_device`: width *
+ * height RGBA32F running sums of `samples` samples; `out_device`: width * height RGBA32F, sums of the same count.  params ==
+ * NULL: the defaults.  Checked before the device is touched, in this order, all BT_ERR_INVALID_ARG: NULL handle, input or
+ * output; samples == 0; zero width or height (or 2^32 pixels and more); output equal to input; radius other than 1 or 2;
+ * rank == 0 or rank > (2 radius + 1)^2 - 1; ratio not finite or < 1; floor not finite or < 0; max_value not finite or <= 0.  A
+ * valid call without a device returns BT_ERR_DEVICE, and so does a frame whose 16 x 16 tiles do not fit one launch (2^24 tiles
+ * and more).
+ * Not provided: host buffers, sharded frames (a shard is tile-major and the window crosses tiles), per-sample clamping inside
+ * the render kernel, the guides or the adaptive moment plane as the statistic. */
+int bt_despeckle_device(bt_despeckle *h, const float *rgba_device, uint32_t samples, float *out_device, uint32_t width, uint32_t height,
+                        const bt_despeckle_params *params, void *stream);
+/* The counts of the last bt_despeckle_device (synchronises its stream).  Both are integers, so they are deterministic.
+ * BT_ERR_INVALID_ARG before any call. */
+int bt_despeckle_poll(bt_despeckle *h, bt_despeckle_stats *out);
+/* For tests, no device and no handle: the whole definition on the host through csrc/bt_despeckle.hpp's own functions,
+ * single-threaded.  The same checks as bt_despeckle_device without the handle.  `stats` may be NULL. */
+int bt_debug_despeckle_host(const float *rgba_host, uint32_t samples, float *out_host, uint32_t width, uint32_t height,
+                            const bt_despeckle_params *params, bt_despeckle_stats *stats);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);

@@ -190,4 +190,28 @@ class Resample {
     bt_resample *h_;
 };
 
+// EXTENSION, not in the reference: a thin delegate of the despeckle stage (bt_despeckle in bendy_hip.h) --
+// rank-order firefly rejection on device-resident frames, ahead of every other stage.  `out` receives SUMS of the input's sample
+// count, not a mean.
+class Despeckle {
+  public:
+    bt_despeckle_params params;
+    Despeckle() : h_(bt_despeckle_new()) { if (!h_) throw Error(bt_last_error_code(), bt_last_error()); bt_despeckle_params_default(&params); }
+    Despeckle(const Despeckle &) = delete;
+    Despeckle &operator=(const Despeckle &) = delete;
+    ~Despeckle() { bt_despeckle_free(h_); }
+    void apply(const float *rgba_device, unsigned samples, float *out_device, unsigned width, unsigned height, void *stream = nullptr) {
+        check(bt_despeckle_device(h_, rgba_device, samples, out_device, width, height, &params, stream));
+    }
+    bt_despeckle_stats poll() {
+        bt_despeckle_stats s;
+        check(bt_despeckle_poll(h_, &s));
+        return s;
+    }
+    bt_despeckle *handle() const { return h_; }
+
+  private:
+    bt_despeckle *h_;
+};
+
 } // namespace bendy
