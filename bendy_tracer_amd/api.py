@@ -195,6 +195,20 @@ class DespeckleStats(C.Structure):  # include/bendy_hip.h `bt_despeckle_stats` (
     _fields_ = [("flagged", C.c_uint32), ("sanitised", C.c_uint32), ("pixels", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _CUpscaleParams(C.Structure):  # include/bendy_hip.h `bt_upscale_params` (extension)
+    _fields_ = [("sigma_depth", C.c_float), ("sigma_albedo", C.c_float), ("normal_squarings", C.c_uint32), ("min_weight", C.c_float),
+                ("max_value", C.c_float)]
+
+
+class _CUpscaleGuides(C.Structure):  # include/bendy_hip.h `bt_upscale_guides` (extension)
+    _fields_ = [("albedo", C.c_void_p), ("albedo_samples", C.c_uint32), ("normal", C.c_void_p), ("normal_samples", C.c_uint32),
+                ("depth", C.c_void_p), ("depth_samples", C.c_uint32)]
+
+
+class UpscaleStats(C.Structure):  # include/bendy_hip.h `bt_upscale_stats` (extension)
+    _fields_ = [("tier2", C.c_uint32), ("tier3", C.c_uint32), ("pixels", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -223,6 +237,8 @@ EXPORTS = [
     "bt_debug_resample_plane", "bt_debug_resample_host",
     "bt_despeckle_params_default", "bt_despeckle_new", "bt_despeckle_free", "bt_despeckle_device", "bt_despeckle_poll",
     "bt_debug_despeckle_host",
+    "bt_upscale_params_default", "bt_upscale_new", "bt_upscale_free", "bt_upscale_device", "bt_upscale_poll",
+    "bt_debug_upscale_weights", "bt_debug_upscale_plane", "bt_debug_upscale_host",
 ]
 
 
@@ -360,6 +376,17 @@ def _load():
     L.bt_despeckle_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(_CDespeckleParams), vp]
     L.bt_despeckle_poll.argtypes = [vp, C.POINTER(DespeckleStats)]
     L.bt_debug_despeckle_host.argtypes = [fp, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.POINTER(_CDespeckleParams), C.POINTER(DespeckleStats)]
+    L.bt_upscale_params_default.argtypes = [C.POINTER(_CUpscaleParams)]
+    L.bt_upscale_new.restype = vp
+    L.bt_upscale_new.argtypes = []
+    L.bt_upscale_free.argtypes = [vp]
+    gp = C.POINTER(_CUpscaleGuides)
+    L.bt_upscale_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, gp, gp, vp, C.c_uint32, C.c_uint32, C.POINTER(_CUpscaleParams), vp]
+    L.bt_upscale_poll.argtypes = [vp, C.POINTER(UpscaleStats)]
+    L.bt_debug_upscale_weights.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), fp, C.POINTER(C.c_uint32)]
+    L.bt_debug_upscale_plane.argtypes = [vp, C.c_uint32, fp, C.c_uint32]
+    L.bt_debug_upscale_host.argtypes = [vp, fp, C.c_uint32, C.c_uint32, C.c_uint32, gp, gp, fp, C.c_uint32, C.c_uint32,
+                                        C.POINTER(_CUpscaleParams), C.POINTER(UpscaleStats)]
     return L
 
 
@@ -1440,6 +1467,173 @@ def despeckle_host(array, samples=1, stats=False, **params):
     st = DespeckleStats()
     _check(lib.bt_debug_despeckle_host(a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), out.ctypes.data_as(C.POINTER(C.c_float)),
                                        a.shape[1], a.shape[0], C.byref(cp), C.byref(st)))
+    return (out, st) if stats else out
+
+
+def _upscale_defaults():
+    p = _CUpscaleParams()
+    lib.bt_upscale_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class UpscaleParams:
+    """`bt_upscale_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_upscale_params_default's value."""
+    sigma_depth: Optional[float] = None
+    sigma_albedo: Optional[float] = None
+    normal_squarings: Optional[int] = None
+    min_weight: Optional[float] = None
+    max_value: Optional[float] = None
+
+    def __post_init__(self):
+        d = _upscale_defaults()
+        for k, _ in _CUpscaleParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+
+    def _c(self):
+        return _CUpscaleParams(float(self.sigma_depth), float(self.sigma_albedo), int(self.normal_squarings), float(self.min_weight),
+                               float(self.max_value))
+
+
+def _guide_triple(guides, what):
+    g = (None, None, None) if guides is None else tuple(guides)
+    if len(g) != 3:
+        raise BendyError(-1, f"{what} must be (albedo, normal, depth), any of them None")
+    return g
+
+
+class Upscale:
+    """`bt_upscale` (include/bendy_hip.h): EXTENSION, not in the reference -- the upscale stage: a small colour frame shown at a
+    larger size, every lo texel weighed by how well its albedo, normal and depth match the output pixel's own (joint bilateral
+    upsampling).  It sits after the denoiser and before the glare stage.  The handle owns the prepared planes, both
+    tables and the tier counter.  Keywords = UpscaleParams fields."""
+
+    def __init__(self, **params):
+        self.params = UpscaleParams(**params)
+        h = lib.bt_upscale_new()
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+        self._plane_dims = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_upscale_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _merged(self, params):
+        return {**{k: getattr(self.params, k) for k, _ in _CUpscaleParams._fields_}, **params}
+
+    def apply(self, color: Buffer, width, height, *, lo=None, hi=None, out: Optional[Buffer] = None, **params) -> Buffer:
+        """The frame of `color` (running sums of `.samples` samples, or a mean with samples = 1) upsampled to width x height ->
+        a Buffer holding the MEAN (samples = 1) with the input's colour space.  `lo` = (albedo, normal, depth) Buffers of the
+        input's size, `hi` the same at width x height; any element may be None, but a guide is given at both sizes or at
+        neither.  Keywords override the handle's UpscaleParams for this call."""
+        p = UpscaleParams(**self._merged(params))
+        width, height = int(width), int(height)
+        lo, hi = _guide_triple(lo, "lo"), _guide_triple(hi, "hi")
+        if color.device == "cpu" or any(g is not None and g.device == "cpu" for g in lo + hi):
+            raise BendyError(-1, "apply needs device-resident buffers (there is no host-buffer variant)")
+        if width < 1 or height < 1:
+            raise BendyError(-1, f"cannot upscale to {width}x{height}")
+        for g in lo:
+            if g is not None and (g.width, g.height) != (color.width, color.height):
+                raise BendyError(-1, f"a lo guide must be {color.width}x{color.height}, the colour frame's size")
+        for g in hi:
+            if g is not None and (g.width, g.height) != (width, height):
+                raise BendyError(-1, f"a hi guide must be {width}x{height}, the output's size")
+        import torch
+        if out is None:
+            out = Buffer(width, height, color.color_space, device=color.device)
+        elif (out.width, out.height) != (width, height) or out.device == "cpu" or out.data.device != color.data.device:
+            raise BendyError(-1, f"out must be a {width}x{height} buffer on the input's device")
+        out.color_space = color.color_space
+        cp, gl, gh = p._c(), _device_guides(lo), _device_guides(hi)
+        _check(lib.bt_upscale_device(self._h, color.data.data_ptr(), max(color.samples, 1), color.width, color.height, C.byref(gl),
+                                     C.byref(gh), out.data.data_ptr(), width, height, C.byref(cp), torch.cuda.current_stream().cuda_stream))
+        self._plane_dims = (color.width, color.height)
+        out.samples = 1
+        return out
+
+    def poll(self) -> UpscaleStats:
+        """bt_upscale_poll (synchronises): the last `apply`'s UpscaleStats -- tier2, tier3, pixels."""
+        st = UpscaleStats()
+        _check(lib.bt_upscale_poll(self._h, C.byref(st)))
+        return st
+
+    def host(self, color, samples, width, height, **kw):
+        """bt_debug_upscale_host on this handle (tests, no device): as `upscale_host`, and the handle keeps the tables the call
+        used, for `weights`."""
+        return upscale_host(color, samples, width, height, _handle=self._h, **self._merged(kw))
+
+    def weights(self, axis):
+        """bt_debug_upscale_weights (tests): the table of axis 0 / "x" or 1 / "y" of the handle's last call ->
+        (first int32 [dst], weights float32 [dst, 8] -- the narrow four, then the wide four --, nearest uint32 [dst])."""
+        axis = {"x": 0, "y": 1}.get(axis, axis)
+        sides = (C.c_uint32 * 2)()
+        n = _check(lib.bt_debug_upscale_weights(self._h, int(axis), sides, None, None, None))
+        dst = int(sides[1])
+        first, w, near = np.zeros(dst, dtype=np.int32), np.zeros((dst, n), dtype=np.float32), np.zeros(dst, dtype=np.uint32)
+        _check(lib.bt_debug_upscale_weights(self._h, int(axis), sides, first.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            w.ctypes.data_as(C.POINTER(C.c_float)), near.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return first, w, near
+
+    def plane(self, which):
+        """bt_debug_upscale_plane (tests; synchronises): a prepared lo plane of the last `apply` as float32 [h, w, 4] -- 0 /
+        "colour": (c.rgb, z), 1 / "normal": (n.xyz, 0), 2 / "albedo": (a.rgb, 0)."""
+        which = {"colour": 0, "color": 0, "normal": 1, "albedo": 2}.get(which, which)
+        n = _check(lib.bt_debug_upscale_plane(self._h, int(which), None, 0))
+        flat = np.zeros(n, dtype=np.float32)
+        _check(lib.bt_debug_upscale_plane(self._h, int(which), flat.ctypes.data_as(C.POINTER(C.c_float)), n))
+        w, h = self._plane_dims
+        return flat.reshape(h, w, 4)
+
+
+def _device_guides(triple):
+    g = _CUpscaleGuides()
+    for name, b in zip(("albedo", "normal", "depth"), triple):
+        if b is not None:
+            setattr(g, name, b.data.data_ptr())
+            setattr(g, name + "_samples", max(b.samples, 1))
+    return g
+
+
+def _host_guides(triple, shape, what, keep):
+    """(albedo, normal, depth), each None, an array [H, W, 4] (a mean) or (array, samples) -> bt_upscale_guides."""
+    g = _CUpscaleGuides()
+    for name, v in zip(("albedo", "normal", "depth"), triple):
+        if v is None:
+            continue
+        arr, n = v if isinstance(v, tuple) else (v, 1)
+        a = np.ascontiguousarray(arr, dtype=np.float32)
+        if a.shape != shape:
+            raise BendyError(-1, f"a {what} guide must be an array of shape {shape}")
+        keep.append(a)
+        setattr(g, name, a.ctypes.data)
+        setattr(g, name + "_samples", int(n))
+    return g
+
+
+def upscale_host(color, samples, width, height, *, lo=None, hi=None, stats=False, _handle=None, **params):
+    """bt_debug_upscale_host (tests, no device): the whole upscale stage on the host through csrc/bt_upscale.hpp's own functions.
+    `color`: float32 [h, w, 4] running sums of `samples`; `lo` / `hi`: (albedo, normal, depth), each None, an array of sums with
+    count 1 or (array, count) -> the mean, float32 [height, width, 4]; with stats=True also the UpscaleStats."""
+    a = np.ascontiguousarray(color, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise BendyError(-1, "upscale_host expects a [H, W, 4] array")
+    width, height = int(width), int(height)
+    out = np.empty((max(height, 0), max(width, 0), 4), dtype=np.float32)
+    keep = []
+    gl = _host_guides(_guide_triple(lo, "lo"), a.shape, "lo", keep)
+    gh = _host_guides(_guide_triple(hi, "hi"), out.shape, "hi", keep)
+    cp = UpscaleParams(**params)._c()
+    st = UpscaleStats()
+    _check(lib.bt_debug_upscale_host(_handle, a.ctypes.data_as(C.POINTER(C.c_float)), int(samples), a.shape[1], a.shape[0], C.byref(gl),
+                                     C.byref(gh), out.ctypes.data_as(C.POINTER(C.c_float)), width, height, C.byref(cp), C.byref(st)))
     return (out, st) if stats else out
 
 

@@ -33,6 +33,11 @@
 // --despeckle RATIO [--despeckle-rank K] [--despeckle-radius R] (extension too; bt_despeckle): the colour sums pass
 // bt_despeckle_device right after the render and before everything else -- under --temporal each frame's sums before the
 // accumulate, with --adaptive the resolved mean (n = 1), because tiles hold different counts.
+// --upscale WxH [--upscale-guide-samples N] (extension too; bt_upscale): the camera aspect is W / H for every render; the
+// progressive loop renders colour and guides at --width x --height through bt_render_guided_device; after it three
+// bt_render_device calls render albedo, normal and depth at W x H (N samples, the same subsample), and the mean that is about to
+// be shown (plain, despeckled, denoised in-line) passes bt_upscale_device ahead of the glare and the display stage.  The
+// screenshot and --hdr then have W x H pixels; --stats-json gains an `upscale` object.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -130,6 +135,9 @@ struct Args {
     bool despeckle = false;
     float despeckle_ratio = 0.0f;
     long despeckle_rank = -1, despeckle_radius = -1;      // -1: bt_despeckle_params_default's
+    bool upscale = false;
+    unsigned upscale_width = 0, upscale_height = 0;
+    long upscale_guide_samples = -1;                      // -1: not given (1)
 };
 
 void usage() {
@@ -164,7 +172,12 @@ void usage() {
                  "       [--despeckle RATIO] [--despeckle-rank 2] [--despeckle-radius 1]   (extension: despeckle stage -- a pixel brighter\n"
                  "                             than RATIO times the rank-th brightest of its neighbours is pulled down to that, on the\n"
                  "                             colour sums right after the render and before every other stage; --output full only,\n"
-                 "                             not with --shard)\n");
+                 "                             not with --shard)\n"
+                 "       [--upscale WxH] [--upscale-guide-samples 1]   (extension: upscale stage -- the render of --width x --height is shown at\n"
+                 "                             W x H, every texel weighed by how well its albedo, normal and depth match those of a\n"
+                 "                             guide-only render of N samples at W x H; after --despeckle and --denoise-inline, before\n"
+                 "                             --glare and the display stage; the screenshot and --hdr then have W x H pixels; --output\n"
+                 "                             full only, not with --shard, --lens, --resample, --denoise, --adaptive or --temporal)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -317,6 +330,21 @@ Args parse(int argc, char **argv) {
                 a.despeckle_radius = n;
             }
         }
+        else if (k == "--upscale") {
+            const std::string spec = val();
+            char tail = 0;
+            if (std::sscanf(spec.c_str(), "%ux%u%c", &a.upscale_width, &a.upscale_height, &tail) != 2 || spec[0] < '0' || spec[0] > '9' ||
+                a.upscale_width == 0 || a.upscale_height == 0 || a.upscale_width > 0x7fffffffu || a.upscale_height > 0x7fffffffu)
+                die("--upscale expects WxH, both positive");
+            a.upscale = true;
+        }
+        else if (k == "--upscale-guide-samples") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.upscale_guide_samples = std::strtol(spec.c_str(), &end, 10);
+            if (spec.empty() || *end != 0 || a.upscale_guide_samples < 1 || a.upscale_guide_samples > 0xffff)
+                die("--upscale-guide-samples expects a count in 1 .. 65535");
+        }
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -358,6 +386,16 @@ Args parse(int argc, char **argv) {
     if (a.despeckle && a.shard_world > 1) die("--despeckle does not apply to a --shard run");
     if (a.despeckle && a.despeckle_rank > (a.despeckle_radius == 2 ? 24 : 8))
         die("--despeckle-rank must not exceed the window's neighbours: 8 at radius 1, 24 at --despeckle-radius 2");
+    if (!a.upscale && a.upscale_guide_samples >= 0) die("--upscale-guide-samples needs --upscale");
+    if (a.upscale && a.output != "full") die("--upscale needs --output full");
+    if (a.upscale && a.shard_world > 1) die("--upscale does not apply to a --shard run");
+    if (a.upscale && a.has_lens) die("--upscale renders its guides in one pass with the colour, which has no builds for --lens");
+    if (a.upscale && a.resample) die("--upscale and --resample exclude each other: one frame is shown at one size");
+    if (a.upscale && a.denoise) die("--upscale takes the guides of the colour pass: use --denoise-inline, not --denoise");
+    if (a.upscale && a.adaptive) die("--upscale does not take the frames of --adaptive, which has no guided variant");
+    if (a.upscale && a.temporal) die("--upscale does not apply to a --temporal run");
+    if (a.upscale && (a.upscale_width < a.width || a.upscale_height < a.height))
+        die("--upscale must not be smaller than --width x --height on either axis: --resample reduces");
     return a;
 }
 
@@ -386,7 +424,9 @@ int main(int argc, char **argv) {
     }
     uint64_t camera = 0;
     check(bt_scene_find_by_tag(scene, "camera", &camera), "find_by_tag(\"camera\")");          // main.rs:216
-    check(bt_scene_set_camera_aspect(scene, camera, (float)args.width / (float)args.height), "aspect");  // :218-223
+    // :218-223; under --upscale every render, small or large, shows the frame of the shown size
+    check(bt_scene_set_camera_aspect(scene, camera, args.upscale ? (float)args.upscale_width / (float)args.upscale_height
+                                                                  : (float)args.width / (float)args.height), "aspect");
     if (args.has_lens) check(bt_scene_set_lens(scene, &args.lens), "bt_scene_set_lens");
     {
         // measurement harness: launch-shape knobs from the environment (the LIBRARY never reads it; this tool does, like
@@ -419,13 +459,15 @@ int main(int argc, char **argv) {
     float *d_frame = nullptr;
     uint8_t *d_rgba8 = nullptr;
     hip_check(hipMalloc((void **)&d_frame, n_px * 16), "hipMalloc");
-    const size_t n_shown = args.resample ? (size_t)args.resample_width * args.resample_height : n_px;     // the frame that is shown
+    const size_t n_shown = args.resample  ? (size_t)args.resample_width * args.resample_height                  // the frame that is shown
+                           : args.upscale ? (size_t)args.upscale_width * args.upscale_height
+                                          : n_px;
     hip_check(hipMalloc((void **)&d_rgba8, n_shown * 4), "hipMalloc");
     hip_check(hipMemcpy(d_frame, init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
 
     // --denoise-inline (extension): the guides' frames and the denoised mean; every call below fills all four in one pass
     float *d_guides[4] = {nullptr, nullptr, nullptr, nullptr};          // albedo, normal, depth, denoised mean
-    if (args.denoise_inline || args.temporal)
+    if (args.denoise_inline || args.temporal || args.upscale)
         for (int g = 0; g < 4; ++g) {
             hip_check(hipMalloc((void **)&d_guides[g], n_px * 16), "hipMalloc");
             hip_check(hipMemcpy(d_guides[g], init.data(), n_px * 16, hipMemcpyHostToDevice), "hipMemcpy");
@@ -502,8 +544,9 @@ int main(int argc, char **argv) {
         gp.strength = args.glare_strength;
         if (args.glare_levels >= 0) gp.levels = (uint32_t)args.glare_levels;
         if (args.glare_spread > 0.0f) gp.spread = args.glare_spread;
-        hip_check(hipMalloc((void **)&d_glare, n_px * 16), "hipMalloc");
-        for (uint32_t m = std::max(args.width, args.height) - 1; m; m >>= 1) ++glare_levels;
+        hip_check(hipMalloc((void **)&d_glare, (args.upscale ? n_shown : n_px) * 16), "hipMalloc");
+        for (uint32_t m = (args.upscale ? std::max(args.upscale_width, args.upscale_height) : std::max(args.width, args.height)) - 1; m; m >>= 1)
+            ++glare_levels;
         glare_levels = std::min(glare_levels, gp.levels);
         char gj[160];
         std::snprintf(gj, sizeof gj, ", \"glare\": {\"strength\": %.9g, \"levels\": %u, \"spread\": %.9g}", gp.strength,
@@ -515,7 +558,10 @@ int main(int argc, char **argv) {
     bt_resample_params rp;
     bt_resample_params_default(&rp);
     float *d_resampled = nullptr;                          // the resampled mean
-    const unsigned shown_w = args.resample ? args.resample_width : args.width, shown_h = args.resample ? args.resample_height : args.height;
+    const unsigned shown_w = args.resample ? args.resample_width : args.upscale ? args.upscale_width : args.width;
+    const unsigned shown_h = args.resample ? args.resample_height : args.upscale ? args.upscale_height : args.height;
+    // the glare stage works on the frame the upscale stage hands on, and otherwise on the render
+    const unsigned glare_w = args.upscale ? args.upscale_width : args.width, glare_h = args.upscale ? args.upscale_height : args.height;
     if (args.resample) {
         resample = bt_resample_new();
         if (!resample) die(bt_last_error());
@@ -608,7 +654,7 @@ int main(int argc, char **argv) {
         rc.samples = std::min(args.samples_per_call, std::max(1u, (args.samples - buffer_samples) / nn));
         rc.sample_base = (buffer_samples + nn - 1) / nn;
         const auto t0 = std::chrono::steady_clock::now();
-        int st = args.denoise_inline
+        int st = args.denoise_inline || args.upscale
                      ? bt_render_guided_device(scene, camera, &cfg, &rc, d_frame, d_guides[0], d_guides[1], d_guides[2], args.width,
                                                args.height, args.seed, nullptr)
                  : sharded ? bt_render_shard_device(scene, camera, &cfg, &rc, d_frame, args.width, args.height, args.shard_rank,
@@ -666,6 +712,7 @@ int main(int argc, char **argv) {
         despeckle_json = sj;
     }
     std::string resample_json;                             // filled once the frame has been resampled
+    std::string upscale_json;                              // filled once the frame has been upscaled
     auto write_stats = [&](const char *display_json) {
         FILE *f = std::fopen(args.stats_json.c_str(), "w");
         if (!f) die("cannot write " + args.stats_json);
@@ -677,11 +724,11 @@ int main(int argc, char **argv) {
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
         std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (despeckle_json + glare_json + resample_json).c_str(), display_json);
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (despeckle_json + upscale_json + glare_json + resample_json).c_str(), display_json);
         std::fclose(f);
     };
     // with the display or the resample stage: once the frame has been shown
-    if (!args.stats_json.empty() && !display && !resample) write_stats("");
+    if (!args.stats_json.empty() && !display && !resample && !args.upscale) write_stats("");
 
     // Ctrl+P (main.rs:275-298)
     std::string shot = args.screenshot;
@@ -773,8 +820,44 @@ int main(int argc, char **argv) {
         shown_samples = 1;                                  // the denoised buffer holds a mean
         std::fprintf(stderr, "denoised with guides of %u samples\n", gs);
     }
+    // --upscale (extension): the three guides again at the shown size, first hit only, then the mean that is about to be shown
+    // passes the upscale stage with the colour pass's own guides as the lo side
+    bt_upscale *upscale = nullptr;
+    float *d_hi[3] = {nullptr, nullptr, nullptr}, *d_upscaled = nullptr;
+    if (args.upscale) {
+        upscale = bt_upscale_new();
+        if (!upscale) die(bt_last_error());
+        std::vector<float> hi_init(n_shown * 4, 0.0f);
+        for (size_t i = 0; i < n_shown; ++i) hi_init[4 * i + 3] = 1.0f;
+        const int aov[3] = {BT_OUTPUT_ALBEDO, BT_OUTPUT_NORMAL, BT_OUTPUT_DEPTH};
+        bt_config gcfg = cfg;
+        bt_render_config grc = rc;
+        grc.samples = args.upscale_guide_samples >= 0 ? (uint32_t)args.upscale_guide_samples : 1u;
+        grc.sample_base = 0;
+        for (int g = 0; g < 3; ++g) {
+            hip_check(hipMalloc((void **)&d_hi[g], n_shown * 16), "hipMalloc");
+            hip_check(hipMemcpy(d_hi[g], hi_init.data(), n_shown * 16, hipMemcpyHostToDevice), "hipMemcpy");
+            gcfg.output = aov[g];
+            check(bt_render_device(scene, camera, &gcfg, &grc, d_hi[g], shown_w, shown_h, args.seed, nullptr), "bt_render_device (upscale guide)");
+        }
+        hip_check(hipMalloc((void **)&d_upscaled, n_shown * 16), "hipMalloc");
+        const uint32_t ls = buffer_samples ? buffer_samples : 1, hs = grc.samples * nn;
+        const bt_upscale_guides lo = {d_guides[0], ls, d_guides[1], ls, d_guides[2], ls}, hi = {d_hi[0], hs, d_hi[1], hs, d_hi[2], hs};
+        check(bt_upscale_device(upscale, d_shown, shown_samples, args.width, args.height, &lo, &hi, d_upscaled, shown_w, shown_h, nullptr, nullptr),
+              "bt_upscale_device");
+        bt_upscale_stats us{};
+        check(bt_upscale_poll(upscale, &us), "bt_upscale_poll");
+        d_shown = d_upscaled;
+        shown_samples = 1;                                  // the upscaled buffer holds a mean
+        std::fprintf(stderr, "upscale: %ux%u -> %ux%u with guides of %u samples: %u pixels took the 4 x 4 footprint, %u fell back to bilinear\n",
+                     args.width, args.height, shown_w, shown_h, hs, us.tier2, us.tier3);
+        char uj[160];
+        std::snprintf(uj, sizeof uj, ", \"upscale\": {\"width\": %u, \"height\": %u, \"tier2\": %u, \"tier3\": %u}", shown_w, shown_h, us.tier2, us.tier3);
+        upscale_json = uj;
+        if (!args.stats_json.empty() && !display) write_stats("");
+    }
     if (glare) {
-        check(bt_glare_device(glare, d_shown, shown_samples, d_glare, args.width, args.height, &gp, nullptr), "bt_glare_device");
+        check(bt_glare_device(glare, d_shown, shown_samples, d_glare, glare_w, glare_h, &gp, nullptr), "bt_glare_device");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         d_shown = d_glare;
         shown_samples = 1;                                  // the glared buffer holds a mean
@@ -847,6 +930,10 @@ int main(int argc, char **argv) {
     if (d_glare) (void)hipFree(d_glare);
     bt_resample_free(resample);
     if (d_resampled) (void)hipFree(d_resampled);
+    bt_upscale_free(upscale);
+    if (d_upscaled) (void)hipFree(d_upscaled);
+    for (float *g : d_hi)
+        if (g) (void)hipFree(g);
     for (float *g : d_guides)
         if (g) (void)hipFree(g);
     bt_scene_free(scene);

@@ -610,8 +610,8 @@ void bt_resample_free(bt_resample *h);
  * x axis, then on the y axis (lanczos3 beyond about 21 : 1, mitchell 32 : 1, tent 64 : 1, box 127 : 1; the message names the axis
  * and the ratio).  A valid call without a device returns BT_ERR_DEVICE, and so does a plane whose 32 x 8 tiles do not fit one
  * launch (2^24 tiles and more).
- * Not provided: host buffers, sharded frames, edge-aware or guide-driven upsampling, resampling of the albedo / normal / depth
- * outputs (step 1 would clamp them), any change to the size the render kernels work at. */
+ * Not provided: host buffers, sharded frames, resampling of the albedo / normal / depth
+ * outputs (step 1 would clamp them), any change to the size the render kernels work at.  Guide-driven upsampling is bt_upscale's. */
 int bt_resample_device(bt_resample *h, const float *rgba_device, uint32_t samples, uint32_t width, uint32_t height, float *out_device,
                        uint32_t out_width, uint32_t out_height, const bt_resample_params *params, void *stream);
 /* For tests: the table of axis 0 (x) or 1 (y) that the handle's last call -- bt_resample_device or bt_debug_resample_host --
@@ -689,6 +689,102 @@ int bt_despeckle_poll(bt_despeckle *h, bt_despeckle_stats *out);
  * single-threaded.  The same checks as bt_despeckle_device without the handle.  `stats` may be NULL. */
 int bt_debug_despeckle_host(const float *rgba_host, uint32_t samples, float *out_host, uint32_t width, uint32_t height,
                             const bt_despeckle_params *params, bt_despeckle_stats *stats);
+
+/* --- EXTENSION -- NOT IN THE REFERENCE: upscale stage -- guide-driven upsampling of a small render --------------
+ * Joint bilateral upsampling (Kopf et al., SIGGRAPH 2007): lighting is rendered at w x h, the albedo, normal and depth guides
+ * (the BT_OUTPUT_ALBEDO / _NORMAL / _DEPTH frames, as bt_denoise* takes them) at w x h AND at the shown size W x H, where a
+ * guide-only render ends at the first hit.  A lo texel contributes to an output pixel by its bilinear weight times how well its
+ * guides match the pixel's own, so a light's radiance is not smeared over the wall next to it.  The stage sits after the
+ * denoiser and before the glare stage, whose halos legitimately cross edges.  It is off unless called, makes no parity claim
+ * and changes neither a render nor any other stage.  The output is a MEAN of W x H, W >= w and H >= h, each axis on its own,
+ * equality allowed.  Pixels are float32 in the order written, without fused multiply-adds; only + - * / and sqrt appear, all
+ * correctly rounded (no exp, no pow); the per-axis tables are float64 on the host (csrc/bt_upscale.hpp has the same lines as
+ * code; tests/upscale_ref.py in numpy):
+ *   1. prepare, at either size, r = 1 / n once per frame:  colour c = the glare stage's step 1 (NaN and negatives -> 0, capped at
+ *      max_value);  fin(v) = |v| < inf ? v : 0;  albedo a = fin(A.rgb * r_a);  normal v = fin(N.rgb * r_n), l = (v.x v.x + v.y v.y) +
+ *      v.z v.z, n = l > 1e-12 ? v / sqrt(l) : 0 -- a zero normal marks a miss;  depth z = fin(Z.r * r_z).  An absent pair is all
+ *      zeros on both sides, which weighs exactly 1.
+ *   2. tables, per axis (src -> dst texels), built once per (src, dst) and kept on the handle:  ratio = (double)src / dst;
+ *      c_i = (i + 0.5) * ratio - 0.5;  x0 = floor(c_i);  f = c_i - x0;  the four taps are x0 - 1 + t, t = 0 .. 3, d_t = t - 1, each
+ *      clamped to [0, src - 1] where it is used, keeping its weight (edge replication);  u1_t = (float)max(0, 1 - |d_t - f|);
+ *      u2_t = (float)max(0, 1 - |d_t - f| * 0.5);  nearest_i = min(src - 1, floor((i + 0.5) * ratio)).
+ *   3. per output pixel p, its 16 taps q, ty outer and tx inner:
+ *        g_n = 1 if both normals are zero, 0 if exactly one is, else m = max((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0) squared
+ *              normal_squarings times;
+ *        g_z = 1 / (1 + t * t),  t = |z_p - z_q| / (sigma_depth * z_p + 1e-6);
+ *        g_a = 1 / (1 + s * k_a),  d = a_p - a_q,  s = (d.x d.x + d.y d.y) + d.z d.z,  k_a = 1 / (sigma_albedo * sigma_albedo) in
+ *              float32 on the host;
+ *        g = (g_n * g_z) * g_a;  s1 = u1y * u1x;  s2 = u2y * u2x;  w1 = s1 * g;  w2 = s2 * g;
+ *        A1 += w1 * c_q, D1 += w1;  A2 += w2 * c_q, D2 += w2;  A0 += s1 * c_q, D0 += s1 -- each as acc = acc + w * c per channel,
+ *        the product rounded, then the sum, over all 16 taps, those of weight 0 too.
+ *   4. out.rgb = A1 / D1 where D1 > min_weight (tier 1: the 2 x 2 bilinear footprint with guides), else A2 / D2 where D2 >
+ *      min_weight (tier 2: the 4 x 4 footprint, for a pixel whose four nearest texels all lie across an edge), else A0 / D0
+ *      (tier 3: plain bilinear).  out.a = C.a at (nearest_x, nearest_y), neither filtered nor divided by n.
+ *   5. the handle counts the pixels of the last call that took tier 2 and tier 3.
+ * With no pair at all the stage is a bilinear resize.  At W x H = w x h, with the same frames as lo and hi guides and no normal
+ * pair, the output is the sanitised mean bit for bit and both counts are 0 (with the normal pair n . n can be 1 - ulp). */
+typedef struct {
+    float sigma_depth;         /* > 0, finite: the relative depth difference at which g_z is 1/2 */
+    float sigma_albedo;        /* > 0, finite: the albedo distance at which g_a is 1/2 */
+    uint32_t normal_squarings; /* 0 .. 6: g_n = max(n_p . n_q, 0)^(2^normal_squarings) */
+    float min_weight;          /* in (0, 1), finite: the D below which a tier is given up */
+    float max_value;           /* > 0, finite: the cap of step 1 */
+} bt_upscale_params;
+/* One frame's guides: running sums of RGBA32F with their sample counts (a mean is 1); NULL marks an absent guide. */
+typedef struct {
+    const float *albedo;
+    uint32_t albedo_samples;
+    const float *normal;
+    uint32_t normal_samples;
+    const float *depth;
+    uint32_t depth_samples;
+} bt_upscale_guides;
+typedef struct {
+    uint32_t tier2;            /* output pixels that took the 4 x 4 footprint */
+    uint32_t tier3;            /* output pixels that fell back to plain bilinear */
+    uint32_t pixels;           /* out_width * out_height of the call */
+    uint32_t reserved;
+} bt_upscale_stats;
+typedef struct bt_upscale bt_upscale;   /* owns the three prepared planes (48 B per texel of w x h), both tables and a counter; one stream at a time */
+/* sigma_depth 0.1, sigma_albedo 0.1, normal_squarings 3 (the 8th power), min_weight 0.01, max_value 65536 (the glare stage's cap).
+ * Starting values; DESIGN.md 19 has the sweep. */
+void bt_upscale_params_default(bt_upscale_params *out);
+/* No device work happens here: the handle allocates on its first bt_upscale_device, on the device current then, and grows on
+ * demand. */
+bt_upscale *bt_upscale_new(void);
+void bt_upscale_free(bt_upscale *h);
+/* Two kernels on `stream` (prepare, upscale), after the counter has been zeroed and a table that changed has been uploaded on
+ * it; returns without synchronising, except that a call which replaces a table first waits for the handle's previous call, whose
+ * upload may still read it.  `color_device`: width * height RGBA32F running sums of `color_samples` samples; `lo`: the guides at
+ * width x height, `hi`: at out_width x out_height, either NULL for none; `out_device`: out_width * out_height RGBA32F, the mean.
+ * params == NULL: the defaults.  Checked before the device is touched, in this order, all BT_ERR_INVALID_ARG: NULL handle, colour
+ * or output; color_samples == 0; a zero side, a side of 2^31 and more or 2^32 pixels and more, on either frame; out_width <
+ * width or out_height < height (bt_resample reduces); output equal to the colour frame or to any guide; a guide present at
+ * one size only; a present guide with 0 samples; sigma_depth, sigma_albedo not finite or <= 0; normal_squarings > 6; min_weight
+ * outside (0, 1); max_value not finite or <= 0.  A valid call without a device returns BT_ERR_DEVICE, and so does a frame whose
+ * 16 x 16 tiles do not fit one launch (2^24 tiles and more).
+ * Not provided: host buffers, sharded frames, downscaling, any change to bt_resample or bt_denoise. */
+int bt_upscale_device(bt_upscale *h, const float *color_device, uint32_t color_samples, uint32_t width, uint32_t height,
+                      const bt_upscale_guides *lo, const bt_upscale_guides *hi, float *out_device, uint32_t out_width, uint32_t out_height,
+                      const bt_upscale_params *params, void *stream);
+/* The counts of the last bt_upscale_device (synchronises its stream).  They are integers, so they are deterministic.
+ * BT_ERR_INVALID_ARG before any call. */
+int bt_upscale_poll(bt_upscale *h, bt_upscale_stats *out);
+/* For tests: the table of axis 0 (x) or 1 (y) that the handle's last call -- bt_upscale_device or bt_debug_upscale_host with a
+ * handle -- built or reused.  Returns 8, the weights per row.  Any pointer may be NULL; `sides` receives {src, dst}, `first` the dst
+ * first taps x0 - 1 (unclamped), `weights` dst rows of u1_0 .. u1_3, u2_0 .. u2_3, `nearest` the dst nearest source indices.
+ * BT_ERR_INVALID_ARG while there is no table. */
+int bt_debug_upscale_weights(bt_upscale *h, int axis, uint32_t *sides, int32_t *first, float *weights, uint32_t *nearest);
+/* For tests: a prepared lo plane of the last bt_upscale_device as width x height float4 -- which = 0: (c.rgb, z), 1: (n.xyz, 0),
+ * 2: (a.rgb, 0).  n == 0 returns the element count, else up to n floats are copied to `host` (synchronises) and the number copied
+ * is returned. */
+int bt_debug_upscale_plane(bt_upscale *h, uint32_t which, float *host, uint32_t n);
+/* For tests, no device: the whole definition on the host through csrc/bt_upscale.hpp's own functions, single-threaded.  The
+ * same checks as bt_upscale_device; `h` may be NULL, else the tables are the handle's (kept for bt_debug_upscale_weights).
+ * `stats` may be NULL. */
+int bt_debug_upscale_host(bt_upscale *h, const float *color_host, uint32_t color_samples, uint32_t width, uint32_t height,
+                          const bt_upscale_guides *lo, const bt_upscale_guides *hi, float *out_host, uint32_t out_width, uint32_t out_height,
+                          const bt_upscale_params *params, bt_upscale_stats *stats);
 
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */

@@ -214,4 +214,29 @@ class Despeckle {
     bt_despeckle *h_;
 };
 
+// EXTENSION, not in the reference: a thin delegate of the upscale stage (bt_upscale in bendy_hip.h) -- guide-driven
+// upsampling of a small device-resident frame of sums to a mean of out_width x out_height, after the denoiser and before the
+// glare stage.  `lo` / `hi`: the guides at the input's and at the output's size, either nullptr for none.
+class Upscale {
+  public:
+    bt_upscale_params params;
+    Upscale() : h_(bt_upscale_new()) { if (!h_) throw Error(bt_last_error_code(), bt_last_error()); bt_upscale_params_default(&params); }
+    Upscale(const Upscale &) = delete;
+    Upscale &operator=(const Upscale &) = delete;
+    ~Upscale() { bt_upscale_free(h_); }
+    void apply(const float *color_device, unsigned samples, unsigned width, unsigned height, const bt_upscale_guides *lo,
+               const bt_upscale_guides *hi, float *out_device, unsigned out_width, unsigned out_height, void *stream = nullptr) {
+        check(bt_upscale_device(h_, color_device, samples, width, height, lo, hi, out_device, out_width, out_height, &params, stream));
+    }
+    bt_upscale_stats poll() {
+        bt_upscale_stats s;
+        check(bt_upscale_poll(h_, &s));
+        return s;
+    }
+    bt_upscale *handle() const { return h_; }
+
+  private:
+    bt_upscale *h_;
+};
+
 } // namespace bendy
