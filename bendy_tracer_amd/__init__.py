@@ -4,9 +4,9 @@ Only what the path needs lives here: `csrc/` (HIP kernels + scene loader + C ABI
 into `libbendy_hip.so`) and `api.py` (host-side mirror of the reference's Rust API).
 Importing the package loads the shared library; a missing library is an ImportError.
 """
-from .api import (Adaptive, AdaptiveParams, AdaptiveStats, BendyError, Buffer, ColorSpace, Comm, Config, DenoiseParams, Denoiser, Despeckle, DespeckleParams, DespeckleStats, Display, DisplayParams, Filter, Glare, GlareParams, Output, RenderConfig, Resample, ResampleParams, Scene, Stats,
-                  Status, Subsample, Temporal, TemporalParams, Tonemap, Tracer, Upscale, UpscaleParams, UpscaleStats, View, denoise, despeckle_host, glare_host, new_shard, reproject, resample_host, shard_floats, tile_owner_map, unshard, upscale_host, write_pfm, write_png)
+from .api import (Adaptive, AdaptiveParams, AdaptiveStats, BendyError, Buffer, ColorSpace, Comm, Compare, CompareParams, CompareStats, Config, DenoiseParams, Denoiser, Despeckle, DespeckleParams, DespeckleStats, Display, DisplayParams, Filter, Glare, GlareParams, Output, RenderConfig, Resample, ResampleParams, Scene, Stats,
+                  Status, Subsample, Temporal, TemporalParams, Tonemap, Tracer, Upscale, UpscaleParams, UpscaleStats, View, compare_host, denoise, despeckle_host, glare_host, new_shard, read_pfm, reproject, resample_host, shard_floats, tile_owner_map, unshard, upscale_host, write_pfm, write_png)
 
-__all__ = ["Adaptive", "AdaptiveParams", "AdaptiveStats", "BendyError", "Buffer", "ColorSpace", "Comm", "Config", "DenoiseParams", "Denoiser", "Despeckle", "DespeckleParams", "DespeckleStats", "Display", "DisplayParams", "Filter", "Glare", "GlareParams", "Output", "RenderConfig", "Resample", "ResampleParams",
-           "Scene", "Stats", "Status", "Subsample", "Temporal", "TemporalParams", "Tonemap", "Tracer", "Upscale", "UpscaleParams", "UpscaleStats", "View", "denoise", "despeckle_host", "glare_host", "new_shard", "reproject", "resample_host", "shard_floats", "tile_owner_map",
+__all__ = ["Adaptive", "AdaptiveParams", "AdaptiveStats", "BendyError", "Buffer", "ColorSpace", "Comm", "Compare", "CompareParams", "CompareStats", "Config", "DenoiseParams", "Denoiser", "Despeckle", "DespeckleParams", "DespeckleStats", "Display", "DisplayParams", "Filter", "Glare", "GlareParams", "Output", "RenderConfig", "Resample", "ResampleParams",
+           "Scene", "Stats", "Status", "Subsample", "Temporal", "TemporalParams", "Tonemap", "Tracer", "Upscale", "UpscaleParams", "UpscaleStats", "View", "compare_host", "denoise", "despeckle_host", "glare_host", "new_shard", "read_pfm", "reproject", "resample_host", "shard_floats", "tile_owner_map",
            "unshard", "upscale_host", "write_pfm", "write_png"]

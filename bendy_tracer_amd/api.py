@@ -209,6 +209,18 @@ class UpscaleStats(C.Structure):  # include/bendy_hip.h `bt_upscale_stats` (exte
     _fields_ = [("tier2", C.c_uint32), ("tier3", C.c_uint32), ("pixels", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _CCompareParams(C.Structure):  # include/bendy_hip.h `bt_compare_params` (extension)
+    _fields_ = [("epsilon", C.c_double), ("peak", C.c_double)]
+
+
+class CompareStats(C.Structure):  # include/bendy_hip.h `bt_compare_stats` (extension)
+    _fields_ = [("pixels", C.c_uint64), ("valid", C.c_uint64), ("nonfinite", C.c_uint64), ("max_index", C.c_uint64),
+                ("mse", C.c_double), ("rel_mse", C.c_double), ("ssim", C.c_double), ("max_abs", C.c_double), ("psnr", C.c_double)]
+
+    def __repr__(self):
+        return "CompareStats(" + ", ".join(f"{k}={getattr(self, k)!r}" for k, _ in self._fields_) + ")"
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -239,6 +251,8 @@ EXPORTS = [
     "bt_debug_despeckle_host",
     "bt_upscale_params_default", "bt_upscale_new", "bt_upscale_free", "bt_upscale_device", "bt_upscale_poll",
     "bt_debug_upscale_weights", "bt_debug_upscale_plane", "bt_debug_upscale_host",
+    "bt_compare_params_default", "bt_compare_new", "bt_compare_free", "bt_compare_device", "bt_compare_poll", "bt_compare_tail",
+    "bt_compare_map_device", "bt_debug_compare_plane", "bt_debug_compare_host", "bt_read_pfm",
 ]
 
 
@@ -387,6 +401,19 @@ def _load():
     L.bt_debug_upscale_plane.argtypes = [vp, C.c_uint32, fp, C.c_uint32]
     L.bt_debug_upscale_host.argtypes = [vp, fp, C.c_uint32, C.c_uint32, C.c_uint32, gp, gp, fp, C.c_uint32, C.c_uint32,
                                         C.POINTER(_CUpscaleParams), C.POINTER(UpscaleStats)]
+    cpp, dp = C.POINTER(_CCompareParams), C.POINTER(C.c_double)
+    L.bt_compare_params_default.argtypes = [cpp]
+    L.bt_compare_new.restype = vp
+    L.bt_compare_new.argtypes = []
+    L.bt_compare_free.argtypes = [vp]
+    L.bt_compare_device.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, cpp, vp]
+    L.bt_compare_poll.argtypes = [vp, C.POINTER(CompareStats)]
+    L.bt_compare_tail.argtypes = [vp, C.c_double, dp, fp]
+    L.bt_compare_map_device.argtypes = [vp, vp, C.c_float, vp]
+    L.bt_debug_compare_plane.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
+    L.bt_debug_compare_host.argtypes = [fp, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.c_uint32, cpp, C.POINTER(CompareStats), fp, dp, dp,
+                                        C.c_uint32, dp, dp, fp]
+    L.bt_read_pfm.argtypes = [C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     return L
 
 
@@ -1638,6 +1665,134 @@ def upscale_host(color, samples, width, height, *, lo=None, hi=None, stats=False
 
 
 _default_denoiser = None
+
+
+def _compare_defaults():
+    p = _CCompareParams()
+    lib.bt_compare_params_default(C.byref(p))
+    return p
+
+
+@dataclass
+class CompareParams:
+    """`bt_compare_params` (include/bendy_hip.h): EXTENSION, not in the reference.  Fields left None take
+    bt_compare_params_default's value."""
+    epsilon: Optional[float] = None
+    peak: Optional[float] = None
+
+    def __post_init__(self):
+        d = _compare_defaults()
+        for k, _ in _CCompareParams._fields_:
+            if getattr(self, k) is None:
+                setattr(self, k, getattr(d, k))
+
+    def _c(self):
+        return _CCompareParams(float(self.epsilon), float(self.peak))
+
+
+class Compare:
+    """`bt_compare` (include/bendy_hip.h): EXTENSION, not in the reference -- the compare stage: how far a test frame is from a
+    reference frame (MSE, relMSE, PSNR, SSIM, the largest difference, the tail share, an error map), bit-identical
+    between the device, the host entry point and numpy.  It measures the chain and changes no frame.  The handle owns three planes
+    (28 B per pixel), a slab of one slot per tile and the histograms.  Keywords = CompareParams fields."""
+
+    def __init__(self, **params):
+        self.params = CompareParams(**params)
+        h = lib.bt_compare_new()
+        if not h:
+            raise BendyError(lib.bt_last_error_code(), lib.bt_last_error().decode("utf-8", "replace"))
+        self._h = C.c_void_p(h)
+        self._size = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.bt_compare_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def measure(self, test: Buffer, reference: Buffer, **params) -> CompareStats:
+        """bt_compare_device, then bt_compare_poll (synchronises): `test` against `reference`, device Buffers of equal size, each
+        running sums of its `.samples` (or a mean with samples = 1); they may be the same Buffer.  Keywords override the handle's
+        CompareParams for this call."""
+        p = CompareParams(**{**{k: getattr(self.params, k) for k, _ in _CCompareParams._fields_}, **params})
+        if test.device == "cpu" or reference.device == "cpu":
+            raise BendyError(-1, "measure needs device-resident buffers (there is no host-buffer variant)")
+        if (test.width, test.height) != (reference.width, reference.height) or test.data.device != reference.data.device:
+            raise BendyError(-1, f"the frames differ: {test.width}x{test.height} against {reference.width}x{reference.height}, or in device")
+        import torch
+        cp = p._c()
+        _check(lib.bt_compare_device(self._h, test.data.data_ptr(), max(test.samples, 1), reference.data.data_ptr(), max(reference.samples, 1),
+                                     test.width, test.height, C.byref(cp), torch.cuda.current_stream().cuda_stream))
+        self._size = (test.width, test.height, test.data.device)
+        return self.poll()
+
+    def poll(self) -> CompareStats:
+        """bt_compare_poll (synchronises): the last `measure`'s CompareStats."""
+        st = CompareStats()
+        _check(lib.bt_compare_poll(self._h, C.byref(st)))
+        return st
+
+    def tail(self, fraction=0.01):
+        """bt_compare_tail (synchronises) -> (share, threshold): the share of the summed error plane that the worst `fraction` of
+        the last `measure`'s valid pixels carry, and the error of the last of them."""
+        share, threshold = C.c_double(0.0), C.c_float(0.0)
+        _check(lib.bt_compare_tail(self._h, float(fraction), C.byref(share), C.byref(threshold)))
+        return share.value, threshold.value
+
+    def map(self, scale=1.0, out=None):
+        """bt_compare_map_device: the last `measure`'s error plane in false colour (black, red, yellow, white at `scale`; a
+        non-finite pixel magenta) -> an RGBA8 device tensor [H, W, 4]."""
+        import torch
+        if self._size is None:
+            raise BendyError(-1, "map before a measure call")
+        w, h, dev = self._size
+        if out is None:
+            out = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        elif tuple(out.shape) != (h, w, 4) or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+            raise BendyError(-1, f"out must be a contiguous uint8 [{h}, {w}, 4] tensor on the frames' device")
+        _check(lib.bt_compare_map_device(self._h, out.data_ptr(), float(scale), torch.cuda.current_stream().cuda_stream))
+        return out
+
+    def plane(self, which):
+        """bt_debug_compare_plane (tests; synchronises): 0 / "E" -> float32 [h, w]; 1 / "v" -> float64 [h, w, 2]; 2 / "s" ->
+        float64 [h, w]."""
+        which = {"E": 0, "v": 1, "s": 2}.get(which, which)
+        n = _check(lib.bt_debug_compare_plane(self._h, int(which), None, 0))
+        flat = np.empty(n, dtype=np.float32 if which == 0 else np.float64)
+        _check(lib.bt_debug_compare_plane(self._h, int(which), flat.ctypes.data_as(C.c_void_p), n))
+        w, h, _ = self._size
+        return flat.reshape(h, w, 2) if which == 1 else flat.reshape(h, w)
+
+
+def compare_host(test, reference, test_samples=1, reference_samples=1, tail=(), **params):
+    """bt_debug_compare_host (tests, no device): the whole compare stage on the host through csrc/bt_compare.hpp's own functions.
+    `test`, `reference`: float32 [H, W, 4] running sums -> (CompareStats, E float32 [H, W], v float64 [H, W, 2], s float64 [H, W],
+    [(share, threshold) for each fraction of `tail`])."""
+    a = np.ascontiguousarray(test, dtype=np.float32)
+    b = np.ascontiguousarray(reference, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape != b.shape:
+        raise BendyError(-1, "compare_host expects two [H, W, 4] arrays of one shape")
+    h, w = a.shape[:2]
+    E, V, S = np.empty((h, w), dtype=np.float32), np.empty((h, w, 2), dtype=np.float64), np.empty((h, w), dtype=np.float64)
+    fr = np.asarray(list(tail), dtype=np.float64)
+    shares, thresholds = np.zeros(len(fr), dtype=np.float64), np.zeros(len(fr), dtype=np.float32)
+    cp = CompareParams(**params)._c()
+    st = CompareStats()
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    _check(lib.bt_debug_compare_host(a.ctypes.data_as(fp), int(test_samples), b.ctypes.data_as(fp), int(reference_samples), w, h, C.byref(cp),
+                                     C.byref(st), E.ctypes.data_as(fp), V.ctypes.data_as(dp), S.ctypes.data_as(dp), len(fr),
+                                     fr.ctypes.data_as(dp), shares.ctypes.data_as(dp), thresholds.ctypes.data_as(fp)))
+    return st, E, V, S, [(float(s), float(t)) for s, t in zip(shares, thresholds)]
+
+
+def read_pfm(path):
+    """bt_read_pfm -> (float32 [H, W, 4] with the rows top-down and alpha 1, width, height)."""
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    _check(lib.bt_read_pfm(os.fsencode(path), None, 0, C.byref(w), C.byref(h)))
+    a = np.empty((h.value, w.value, 4), dtype=np.float32)
+    _check(lib.bt_read_pfm(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_float)), a.size, C.byref(w), C.byref(h)))
+    return a, w.value, h.value
 
 
 def denoise(color: Buffer, albedo: Optional[Buffer] = None, normal: Optional[Buffer] = None, depth: Optional[Buffer] = None,

@@ -38,6 +38,11 @@
 // bt_render_device calls render albedo, normal and depth at W x H (N samples, the same subsample), and the mean that is about to
 // be shown (plain, despeckled, denoised in-line) passes bt_upscale_device ahead of the glare and the display stage.  The
 // screenshot and --hdr then have W x H pixels; --stats-json gains an `upscale` object.
+// --compare TRUTH.pfm [--compare-tail F] [--compare-map PATH.png [--compare-map-scale S]] (extension too; bt_compare): the
+// scene-linear mean that --hdr would write -- after every stage, before the display stage -- is measured against the file, which
+// must have the shown frame's size: MSE, relMSE, PSNR, SSIM, the largest difference, and the share of the error carried by the worst
+// F (0.01 unless told) of the pixels.  The figures are printed and --stats-json gains a `compare` object; --compare-map saves the
+// error plane in false colour, white at S (1 unless told).  It changes no output.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -137,6 +142,9 @@ struct Args {
     long despeckle_rank = -1, despeckle_radius = -1;      // -1: bt_despeckle_params_default's
     bool upscale = false;
     unsigned upscale_width = 0, upscale_height = 0;
+    std::string compare, compare_map;                    // --compare TRUTH.pfm, --compare-map PATH.png
+    double compare_tail = -1.0;                          // < 0: not given (0.01)
+    float compare_map_scale = -1.0f;                     // < 0: not given (1)
     long upscale_guide_samples = -1;                      // -1: not given (1)
 };
 
@@ -177,7 +185,10 @@ void usage() {
                  "                             W x H, every texel weighed by how well its albedo, normal and depth match those of a\n"
                  "                             guide-only render of N samples at W x H; after --despeckle and --denoise-inline, before\n"
                  "                             --glare and the display stage; the screenshot and --hdr then have W x H pixels; --output\n"
-                 "                             full only, not with --shard, --lens, --resample, --denoise, --adaptive or --temporal)\n");
+                 "                             full only, not with --shard, --lens, --resample, --denoise, --adaptive or --temporal)\n"
+                 "       [--compare TRUTH.pfm] [--compare-tail 0.01] [--compare-map PATH.png] [--compare-map-scale 1]\n"
+                 "                            (extension: MSE, relMSE, PSNR, SSIM and the tail share of the frame --hdr would write\n"
+                 "                             against a PFM of the same size; --output full only, not with --shard)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -345,6 +356,20 @@ Args parse(int argc, char **argv) {
             if (spec.empty() || *end != 0 || a.upscale_guide_samples < 1 || a.upscale_guide_samples > 0xffff)
                 die("--upscale-guide-samples expects a count in 1 .. 65535");
         }
+        else if (k == "--compare") a.compare = val();
+        else if (k == "--compare-map") a.compare_map = val();
+        else if (k == "--compare-tail") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.compare_tail = std::strtod(spec.c_str(), &end);
+            if (spec.empty() || *end != 0 || !(a.compare_tail > 0.0 && a.compare_tail <= 1.0)) die("--compare-tail expects a fraction in (0, 1]");
+        }
+        else if (k == "--compare-map-scale") {
+            const std::string spec = val();
+            char *end = nullptr;
+            a.compare_map_scale = std::strtof(spec.c_str(), &end);
+            if (spec.empty() || *end != 0 || !(a.compare_map_scale > 0.0f && a.compare_map_scale < 3.0e38f)) die("--compare-map-scale expects a finite value > 0");
+        }
         else if (k == "--help" || k == "-h") { usage(); std::exit(0); }
         else { usage(); die("unknown argument " + k); }
     }
@@ -396,6 +421,20 @@ Args parse(int argc, char **argv) {
     if (a.upscale && a.temporal) die("--upscale does not apply to a --temporal run");
     if (a.upscale && (a.upscale_width < a.width || a.upscale_height < a.height))
         die("--upscale must not be smaller than --width x --height on either axis: --resample reduces");
+    if (a.compare.empty() && (a.compare_tail >= 0.0 || !a.compare_map.empty() || a.compare_map_scale >= 0.0f))
+        die("--compare-tail, --compare-map and --compare-map-scale need --compare");
+    if (a.compare_map.empty() && a.compare_map_scale >= 0.0f) die("--compare-map-scale needs --compare-map");
+    if (!a.compare.empty() && a.output != "full") die("--compare needs --output full");
+    if (!a.compare.empty() && a.shard_world > 1) die("--compare does not apply to a --shard run");
+    if (!a.compare.empty()) {                            // the file's size against the shown frame's, before any device work
+        const unsigned sw = a.resample ? a.resample_width : a.upscale ? a.upscale_width : a.width;
+        const unsigned sh = a.resample ? a.resample_height : a.upscale ? a.upscale_height : a.height;
+        uint32_t tw = 0, th = 0;
+        if (bt_read_pfm(a.compare.c_str(), nullptr, 0, &tw, &th) < 0) die(std::string("--compare: ") + bt_last_error());
+        if (tw != sw || th != sh)
+            die("--compare: " + a.compare + " has " + std::to_string(tw) + "x" + std::to_string(th) + " pixels, the shown frame " + std::to_string(sw) +
+                "x" + std::to_string(sh));
+    }
     return a;
 }
 
@@ -713,6 +752,7 @@ int main(int argc, char **argv) {
     }
     std::string resample_json;                             // filled once the frame has been resampled
     std::string upscale_json;                              // filled once the frame has been upscaled
+    std::string compare_json;                              // filled once the frame has been compared
     auto write_stats = [&](const char *display_json) {
         FILE *f = std::fopen(args.stats_json.c_str(), "w");
         if (!f) die("cannot write " + args.stats_json);
@@ -724,7 +764,7 @@ int main(int argc, char **argv) {
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
         std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (despeckle_json + upscale_json + glare_json + resample_json).c_str(), display_json);
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (despeckle_json + upscale_json + glare_json + resample_json + compare_json).c_str(), display_json);
         std::fclose(f);
     };
     // with the display or the resample stage: once the frame has been shown
@@ -879,6 +919,53 @@ int main(int argc, char **argv) {
         std::snprintf(rj, sizeof rj, ", \"resample\": {\"width\": %u, \"height\": %u, \"filter\": \"%s\", \"taps_x\": %d, \"taps_y\": %d}", shown_w,
                       shown_h, names[rp.filter], taps_x, taps_y);
         resample_json = rj;
+        if (!args.stats_json.empty() && !display) write_stats("");
+    }
+    // --compare (extension): the frame --hdr would write against the truth; nothing below reads what this writes
+    if (!args.compare.empty()) {
+        std::vector<float> truth(n_shown * 4);
+        uint32_t tw = 0, th = 0;
+        check(bt_read_pfm(args.compare.c_str(), truth.data(), truth.size(), &tw, &th), "bt_read_pfm");
+        if (tw != shown_w || th != shown_h) die("--compare: " + args.compare + " changed its size");
+        float *d_truth = nullptr;
+        hip_check(hipMalloc((void **)&d_truth, n_shown * 16), "hipMalloc");
+        hip_check(hipMemcpy(d_truth, truth.data(), n_shown * 16, hipMemcpyHostToDevice), "hipMemcpy");
+        bt_compare *cmp = bt_compare_new();
+        if (!cmp) die(bt_last_error());
+        bt_compare_params cp;
+        bt_compare_params_default(&cp);
+        bt_compare_stats cs{};
+        check(bt_compare_device(cmp, d_shown, shown_samples, d_truth, 1, shown_w, shown_h, &cp, nullptr), "bt_compare_device");
+        check(bt_compare_poll(cmp, &cs), "bt_compare_poll");
+        const double fraction = args.compare_tail >= 0.0 ? args.compare_tail : 0.01;
+        double share = 0.0;
+        check(bt_compare_tail(cmp, fraction, &share, nullptr), "bt_compare_tail");
+        const unsigned long long max_x = cs.max_index % shown_w, max_y = cs.max_index / shown_w;
+        char psnr[40];
+        if (std::isfinite(cs.psnr)) std::snprintf(psnr, sizeof psnr, "%.17g", cs.psnr);
+        else std::snprintf(psnr, sizeof psnr, "null");
+        if (!args.quiet)
+            std::fprintf(stderr, "compare: against %s: MSE %.6g, relMSE %.6g, PSNR %s dB, SSIM %.6f, max |d| %.6g at (%llu, %llu), %llu valid and %llu "
+                         "non-finite pixels, the worst %g of them carry %.4f of the error\n", args.compare.c_str(), cs.mse, cs.rel_mse,
+                         std::isfinite(cs.psnr) ? psnr : "inf", cs.ssim, cs.max_abs, max_x, max_y, (unsigned long long)cs.valid,
+                         (unsigned long long)cs.nonfinite, fraction, share);
+        char cj[640];
+        std::snprintf(cj, sizeof cj, ", \"compare\": {\"mse\": %.17g, \"rel_mse\": %.17g, \"psnr\": %s, \"ssim\": %.17g, \"max_abs\": %.17g, \"max_x\": %llu, "
+                      "\"max_y\": %llu, \"valid\": %llu, \"nonfinite\": %llu, \"tail_fraction\": %.17g, \"tail_share\": %.17g}", cs.mse, cs.rel_mse, psnr,
+                      cs.ssim, cs.max_abs, max_x, max_y, (unsigned long long)cs.valid, (unsigned long long)cs.nonfinite, fraction, share);
+        compare_json = cj;
+        if (!args.compare_map.empty()) {
+            uint8_t *d_map = nullptr;
+            hip_check(hipMalloc((void **)&d_map, n_shown * 4), "hipMalloc");
+            check(bt_compare_map_device(cmp, d_map, args.compare_map_scale >= 0.0f ? args.compare_map_scale : 1.0f, nullptr), "bt_compare_map_device");
+            std::vector<uint8_t> map8(n_shown * 4);
+            hip_check(hipMemcpy(map8.data(), d_map, n_shown * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+            check(bt_write_png(args.compare_map.c_str(), map8.data(), shown_w, shown_h), "bt_write_png (--compare-map)");
+            if (!args.quiet) std::fprintf(stderr, "saved error map to %s\n", args.compare_map.c_str());
+            (void)hipFree(d_map);
+        }
+        bt_compare_free(cmp);
+        (void)hipFree(d_truth);
         if (!args.stats_json.empty() && !display) write_stats("");
     }
     if (display) {

@@ -1,6 +1,6 @@
 // bt_io.cpp -- the callers' side of the path: scene save (serde_json::to_writer_pretty
 // + optional gzip, main.rs:299-313), the built-in default scene (main.rs:107-214) and the PNG
-// screenshot of the 8-bit preview (main.rs:275-298), and the linear frame as a Portable Float Map (extension: bt_write_pfm).
+// screenshot of the 8-bit preview (main.rs:275-298), and the linear frame as a Portable Float Map, written and read (extensions: bt_write_pfm, bt_read_pfm).
 // No GPU work here.
 #include <zlib.h>
 
@@ -268,6 +268,67 @@ void write_pfm(const std::string &path, const float *rgba, uint32_t w, uint32_t 
         ok = std::fwrite(row.data(), sizeof(float), row.size(), f) == row.size();      // the hosts this library runs on are little-endian
     }
     if (std::fclose(f) != 0 || !ok) throw Error{BT_ERR_IO, "write error on " + path};
+}
+
+// The inverse of write_pfm, and of any other writer's file: "PF" (colour) or "Pf" (grey, replicated to three channels), the two
+// sides, then the scale, whose sign gives the byte order (negative: little-endian) and whose magnitude is ignored; one white-space
+// character; the rows bottom to top.  `rgba` receives them top-down with alpha 1; with rgba == nullptr only the size is read.
+void read_pfm(const std::string &path, float *rgba, size_t capacity_floats, uint32_t &w, uint32_t &h) {
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) throw Error{BT_ERR_IO, "cannot open " + path};
+    struct Closer {
+        FILE *f;
+        ~Closer() { std::fclose(f); }
+    } closer{f};
+    // three white-space separated header fields after the magic, each of a bounded length
+    auto token = [&](std::string &out) {
+        out.clear();
+        int c = std::fgetc(f);
+        while (c == ' ' || c == '\t' || c == '\n' || c == '\r') c = std::fgetc(f);
+        while (c != EOF && c != ' ' && c != '\t' && c != '\n' && c != '\r') {
+            if (out.size() >= 32) throw Error{BT_ERR_PARSE, path + ": malformed PFM header"};
+            out += (char)c;
+            c = std::fgetc(f);
+        }
+        if (c == EOF || out.empty()) throw Error{BT_ERR_PARSE, path + ": truncated PFM header"};
+    };
+    std::string magic, sw, sh, ss;
+    token(magic);
+    if (magic != "PF" && magic != "Pf") throw Error{BT_ERR_PARSE, path + ": not a PFM file (no PF / Pf magic)"};
+    const size_t channels = magic == "PF" ? 3 : 1;
+    token(sw);
+    token(sh);
+    token(ss);                           // consumes the single white-space character that ends the header
+    char *end = nullptr;
+    const unsigned long long lw = std::strtoull(sw.c_str(), &end, 10);
+    const bool w_ok = *end == 0 && sw[0] >= '0' && sw[0] <= '9';
+    const unsigned long long lh = std::strtoull(sh.c_str(), &end, 10);
+    const bool h_ok = *end == 0 && sh[0] >= '0' && sh[0] <= '9';
+    const double scale = std::strtod(ss.c_str(), &end);
+    if (!w_ok || !h_ok || *end != 0 || !(scale != 0.0) || !std::isfinite(scale))
+        throw Error{BT_ERR_PARSE, path + ": malformed PFM header"};
+    if (lw == 0 || lh == 0 || lw > 0x7fffffffull || lh > 0x7fffffffull || lw * lh > 0xffffffffull)
+        throw Error{BT_ERR_PARSE, path + ": a PFM of " + sw + "x" + sh + " pixels is zero-sized or too large"};
+    w = (uint32_t)lw;
+    h = (uint32_t)lh;
+    if (!rgba) return;
+    if ((unsigned long long)capacity_floats < lw * lh * 4)
+        throw Error{BT_ERR_INVALID_ARG, "a " + sw + "x" + sh + " PFM needs room for " + std::to_string(lw * lh * 4) + " floats"};
+    const bool swap = scale > 0.0;       // big-endian file; the hosts this library runs on are little-endian
+    std::vector<float> row((size_t)w * channels);
+    for (uint32_t y = h; y-- > 0;) {
+        if (std::fread(row.data(), sizeof(float), row.size(), f) != row.size()) throw Error{BT_ERR_PARSE, path + ": truncated PFM data"};
+        float *dst = rgba + (size_t)y * w * 4;
+        for (uint32_t x = 0; x < w; ++x) {
+            for (size_t c = 0; c < 3; ++c) {
+                uint32_t u;
+                std::memcpy(&u, &row[(size_t)x * channels + (channels == 3 ? c : 0)], 4);
+                if (swap) u = (u >> 24) | ((u >> 8) & 0xff00u) | ((u << 8) & 0xff0000u) | (u << 24);
+                std::memcpy(&dst[(size_t)x * 4 + c], &u, 4);
+            }
+            dst[(size_t)x * 4 + 3] = 1.0f;
+        }
+    }
 }
 
 } // namespace bt

@@ -100,6 +100,7 @@ void write_text_file(const std::string &path, const std::string &text);   // gzi
 std::string default_scene_json();                                           // main.rs:107-214
 void write_png(const std::string &path, const uint8_t *rgba, uint32_t w, uint32_t h);
 void write_pfm(const std::string &path, const float *rgba, uint32_t w, uint32_t h, uint32_t samples);   // extension
+void read_pfm(const std::string &path, float *rgba, size_t capacity_floats, uint32_t &w, uint32_t &h);        // extension
 
 // rand 0.8.5 UniformFloat::new / new_inclusive scale
 float uniform_scale(float lo, float hi, bool inclusive);

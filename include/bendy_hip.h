@@ -786,6 +786,83 @@ int bt_debug_upscale_host(bt_upscale *h, const float *color_host, uint32_t color
                           const bt_upscale_guides *lo, const bt_upscale_guides *hi, float *out_host, uint32_t out_width, uint32_t out_height,
                           const bt_upscale_params *params, bt_upscale_stats *stats);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: compare stage -- deterministic image-error metrics on the device --------
+ * How far a test frame X is from a reference frame Y: MSE, relMSE, PSNR, SSIM, the largest difference, the share of the error
+ * that the worst pixels carry, and a false-colour error map.  It measures the chain and is no part of it: nothing here changes a
+ * frame.  Both frames are width * height RGBA32F running sums on the device with their sample counts (a mean has count 1); alpha
+ * is ignored; the two may be the same pointer.  Everything is float64 unless marked float32, computed in the order written
+ * (-ffp-contract=off) with + - * /, max and compares only, so the device, the host entry point and numpy agree bit for bit
+ * (csrc/bt_compare.hpp has the same lines as code; tests/compare_ref.py in numpy):
+ *   1. point      float32: r = 1 / n; x = X.rgb * r_x, y = Y.rgb * r_y.  A pixel is BAD if any of the six fails |v| < inf: it
+ *                 counts in `nonfinite`, is not in `valid`, and all its terms are 0.  Else, in float64, per channel d = x - y,
+ *                 e = d d, q = e / (y y + epsilon); se = (e.r + e.g) + e.b; re = (q.r + q.g) + q.b; m = max |d|.  The error
+ *                 plane, float32: E = re < FLT_MAX ? (float)re : FLT_MAX; a bad pixel holds -0.0f (== 0, sign bit set).
+ *   2. structure  float32: Yf = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z on x and on y; Yc = Yf > 0 ? min(Yf, FLT_MAX) : 0; a bad
+ *                 pixel holds 0 on both sides.  float64: v = Yc / (1 + Yc).
+ *   3. SSIM       11 taps of sigma 1.5 (literal weights); vx, vy, vx vx, vy vy, vx vy are blurred along x, then along y, with
+ *                 edge replication, acc = acc + W[k] a[clamp(i + k - 5)] from acc = 0; sx = xx - mx mx, sy = yy - my my, cxy =
+ *                 xy - mx my; s = ((2 (mx my) + C1)(2 cxy + C2)) / (((mx mx + my my) + C1)((sx + sy) + C2)), C1 = 1e-4, C2 = 9e-4.
+ *   4. sums       per 16 x 16 tile a fixed tree over the 256 slots (stride 128, 64 .. 1), 0.0 outside the frame; the tiles'
+ *                 partials are added one after another in tile order on the host.  No float atomic anywhere.
+ *   5. results    below.  psnr = 10 log10(peak peak / mse) is formed on the host and is the one field that depends on a math
+ *                 library; +inf for mse == 0.
+ * One handle serves one stream at a time. */
+typedef struct bt_compare_params {
+    double epsilon;         /* relMSE's denominator offset; finite and > 0 */
+    double peak;            /* PSNR's peak value; finite and > 0 */
+} bt_compare_params;
+typedef struct bt_compare_stats {
+    uint64_t pixels, valid, nonfinite;
+    uint64_t max_index;     /* the smallest y * width + x that attains max_abs */
+    double mse;             /* S_se / (3 valid); 0 without a valid pixel */
+    double rel_mse;         /* S_re / (3 valid); 0 without a valid pixel */
+    double ssim;            /* S_s / pixels */
+    double max_abs;
+    double psnr;
+} bt_compare_stats;
+typedef struct bt_compare bt_compare;   /* owns the planes E, (vx, vy) and s (28 B per pixel), a slab of one slot per tile and the histograms */
+
+/* epsilon 0.01, peak 1.0. */
+void bt_compare_params_default(bt_compare_params *out);
+/* No device work happens here: the handle allocates on its first bt_compare_device, on the device current then, and grows on
+ * demand, never per call. */
+bt_compare *bt_compare_new(void);
+void bt_compare_free(bt_compare *h);
+/* Two kernels on `stream` (point, SSIM); returns without synchronising.  Checked before the device is touched, in this order, all
+ * BT_ERR_INVALID_ARG: NULL handle, frame or params; a sample count of 0; a zero side, a side of 2^31 and more or 2^32 pixels and
+ * more; epsilon, then peak, not finite or <= 0.  A valid call without a device returns BT_ERR_DEVICE, and so does a frame whose
+ * 16 x 16 tiles do not fit one launch (2^24 tiles and more). */
+int bt_compare_device(bt_compare *h, const float *test_device, uint32_t test_samples, const float *ref_device, uint32_t ref_samples,
+                      uint32_t width, uint32_t height, const bt_compare_params *params, void *stream);
+/* The results of the last bt_compare_device (synchronises its stream; the frame sums are formed here, in tile order).
+ * BT_ERR_INVALID_ARG before any call. */
+int bt_compare_poll(bt_compare *h, bt_compare_stats *out);
+/* The share of S_all = sum E that the worst `fraction` of the valid pixels of the last call carry (synchronises):
+ * k = clamp(ceil(fraction valid), 1, valid); T = the k-th largest E, found exactly by a radix select over the float32 bit patterns
+ * (three passes of 11, 11 and 10 bits, a 2 048-bin integer histogram each); c_gt = #(E > T), S_gt = the sum of (double)E over
+ * those; share = (S_gt + (k - c_gt) (double)T) / S_all, 0 when S_all == 0.  `threshold` receives T.  Either pointer may be NULL.
+ * BT_ERR_INVALID_ARG for a fraction outside (0, 1] and before any call. */
+int bt_compare_tail(bt_compare *h, double fraction, double *share, float *threshold);
+/* The error plane of the last call as RGBA8 on `stream` (one kernel; does not synchronise): in float32 t = min(E / scale, 1),
+ * r = min(3 t, 1), g = clamp(3 t - 1, 0, 1), b = clamp(3 t - 2, 0, 1), each stored as (uint8)(v 255 + 0.5), alpha 255; a bad
+ * pixel is (255, 0, 255).  BT_ERR_INVALID_ARG for a NULL pointer, a scale that is not finite or not > 0, and before any call. */
+int bt_compare_map_device(bt_compare *h, uint8_t *rgba8_device, float scale, void *stream);
+/* For tests: a plane of the last bt_compare_device -- which = 0: E, float32; 1: (vx, vy), float64 pairs; 2: s, float64.  n == 0
+ * returns the element count (two per pixel for plane 1), else up to n elements are copied to `host` (synchronises) and the number
+ * copied is returned. */
+int bt_debug_compare_plane(bt_compare *h, uint32_t which, void *host, uint32_t n);
+/* For tests, no device: the whole definition on the host through csrc/bt_compare.hpp's own functions, single-threaded.  The same
+ * checks as bt_compare_device.  `stats` and the planes (width * height floats, pairs of doubles, doubles) may be NULL; with
+ * n_tail > 0 the tail of each of `fractions` is written to `shares` and `thresholds`. */
+int bt_debug_compare_host(const float *test_host, uint32_t test_samples, const float *ref_host, uint32_t ref_samples, uint32_t width,
+                          uint32_t height, const bt_compare_params *params, bt_compare_stats *stats, float *e_host, double *v_host,
+                          double *s_host, uint32_t n_tail, const double *fractions, double *shares, float *thresholds);
+/* Reads a Portable Float Map: "PF" (colour) or "Pf" (grey, replicated to three channels), either byte order by the sign of the
+ * scale, whose magnitude is ignored.  `rgba_host` receives the rows top-down (undoing bt_write_pfm's flip) as RGBA with alpha 1;
+ * with rgba_host == NULL only *width and *height are written.  A missing file -> BT_ERR_IO; a malformed or truncated one ->
+ * BT_ERR_PARSE; capacity_floats < 4 width height -> BT_ERR_INVALID_ARG. */
+int bt_read_pfm(const char *path, float *rgba_host, size_t capacity_floats, uint32_t *width, uint32_t *height);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);

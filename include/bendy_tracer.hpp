@@ -239,4 +239,34 @@ class Upscale {
     bt_upscale *h_;
 };
 
+// EXTENSION, not in the reference: a thin delegate of the compare stage (bt_compare in bendy_hip.h) -- deterministic
+// image-error metrics of a device-resident test frame against a reference frame of the same size.  It changes no frame.
+class Compare {
+  public:
+    bt_compare_params params;
+    Compare() : h_(bt_compare_new()) { if (!h_) throw Error(bt_last_error_code(), bt_last_error()); bt_compare_params_default(&params); }
+    Compare(const Compare &) = delete;
+    Compare &operator=(const Compare &) = delete;
+    ~Compare() { bt_compare_free(h_); }
+    // enqueues and polls
+    bt_compare_stats measure(const float *test_device, unsigned test_samples, const float *ref_device, unsigned ref_samples, unsigned width,
+                             unsigned height, void *stream = nullptr) {
+        check(bt_compare_device(h_, test_device, test_samples, ref_device, ref_samples, width, height, &params, stream));
+        bt_compare_stats s;
+        check(bt_compare_poll(h_, &s));
+        return s;
+    }
+    // the share of the summed error plane carried by the worst `fraction` of the valid pixels; *threshold: the last of them
+    double tail(double fraction = 0.01, float *threshold = nullptr) {
+        double share = 0.0;
+        check(bt_compare_tail(h_, fraction, &share, threshold));
+        return share;
+    }
+    void map(unsigned char *rgba8_device, float scale = 1.0f, void *stream = nullptr) { check(bt_compare_map_device(h_, rgba8_device, scale, stream)); }
+    bt_compare *handle() const { return h_; }
+
+  private:
+    bt_compare *h_;
+};
+
 } // namespace bendy
