@@ -234,7 +234,7 @@ EXPORTS = [
     "bt_comm_unique_id", "bt_comm_init", "bt_comm_free", "bt_comm_rank", "bt_comm_world", "bt_allgather_shards_device",
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
-    "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_set_object",
+    "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_block_order", "bt_debug_block_order_device", "bt_debug_set_object",
     "bt_debug_plan_launch",
     "bt_render_guided_device", "bt_adaptive_params_default", "bt_adaptive_new", "bt_adaptive_free", "bt_adaptive_reset",
     "bt_render_adaptive_device", "bt_adaptive_poll", "bt_adaptive_counts", "bt_adaptive_errors", "bt_debug_adaptive_moments",
@@ -299,6 +299,8 @@ def _load():
     L.bt_debug_block_masks_device.argtypes = L.bt_debug_primary_mask.argtypes
     L.bt_debug_mask_key.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32]
+    L.bt_debug_block_order.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.bt_debug_block_order_device.argtypes = L.bt_debug_block_order.argtypes
     L.bt_debug_plan_launch.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
                                        C.POINTER(Stats)]
@@ -784,6 +786,18 @@ class Tracer:
         _check(lib.bt_debug_block_masks_device(scene._h, camera, C.byref(c), C.byref(r), width, height, slices, rank, world,
                                                out.ctypes.data_as(C.POINTER(C.c_uint64)), n))
         return out
+
+    @staticmethod
+    def block_order(masks, device=False):
+        """bt_debug_block_order / bt_debug_block_order_device (tests): the order in which a launch takes blocks with these
+        masks -- non-zero masks first, each part ascending -- and the counts (n_live, n_empty); device=True: as the GPU
+        kernel writes them."""
+        m = np.ascontiguousarray(masks, dtype=np.uint64)
+        order, header = np.zeros(m.size, dtype=np.uint32), np.zeros(2, dtype=np.uint32)
+        fn = lib.bt_debug_block_order_device if device else lib.bt_debug_block_order
+        _check(fn(m.ctypes.data_as(C.POINTER(C.c_uint64)), m.size, order.ctypes.data_as(C.POINTER(C.c_uint32)),
+                  header.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return order, (int(header[0]), int(header[1]))
 
     def mask_key(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1) -> bytes:
         """bt_debug_mask_key (tests): the key under which the handle would keep these masks between renders."""

@@ -82,6 +82,7 @@ struct bt_scene {
     // per-block sphere masks of the last launch that read them (bt_cull.hpp block_mask): grow-only, reused as long as the key
     // -- everything the masks depend on -- stays what it was (a progressive sequence, the launches of one deep render)
     DeviceArray<uint64_t> d_block_masks;
+    DeviceArray<uint32_t> d_block_order;   // {n_live, n_empty, order[]} made from those masks (bt_cull.hpp block_order): same key
     btcull::MaskKey masks_for{};   // valid = 0: none
     uint64_t rows_generation = 0;  // bumped wherever d_sphere_rows is uploaded
     DeviceArray<float> d_host_frame;   // device copy of the caller's host buffer (bt_render), kept between calls
@@ -109,6 +110,7 @@ struct bt_scene {
         d_scratch.release();
         d_host_frame.release();
         d_block_masks.release();
+        d_block_order.release();
         masks_for = btcull::MaskKey{};
         scratch_small_streak = 0;
     }
@@ -365,22 +367,26 @@ int upload_lens_prims(bt_scene *s, BtLaunch &P) {
     return 0;
 }
 
-// One mask per block, the same for every launch of this render (blocks and slices do not change with the sample range) and
-// for every later render with the same key; computed on this stream, inside the timed region.
+// One mask per block and the block order made from the masks, the same for every launch of this render (blocks and slices do
+// not change with the sample range) and for every later render with the same key; computed on this stream, inside the timed
+// region, the order kernel behind the mask kernel.
 int ensure_block_masks(bt_scene *s, BtLaunch &P, uint32_t n_blocks, hipStream_t stream) {
     btcull::MaskKey key;
     btcull::mask_key(key, P, n_blocks, s->rows_generation, (const void *)stream);
     if (!bt_mask_cache_enabled() || std::memcmp(&key, &s->masks_for, sizeof key) != 0) {
-        if (s->d_block_masks.count < n_blocks) {
-            if (s->d_block_masks.ptr) BT_HIP(hipDeviceSynchronize());    // earlier launches, on whichever stream, may still read the old buffer
+        if (s->d_block_masks.count < n_blocks || s->d_block_order.count < (size_t)n_blocks + BT_ORDER_HEADER) {
+            if (s->d_block_masks.ptr) BT_HIP(hipDeviceSynchronize());    // earlier launches, on whichever stream, may still read the old buffers
             s->masks_for = btcull::MaskKey{};
             BT_HIP(s->d_block_masks.allocate(n_blocks));
+            BT_HIP(s->d_block_order.allocate((size_t)n_blocks + BT_ORDER_HEADER));
         }
-        s->masks_for = btcull::MaskKey{};          // (stays invalid if the launch fails)
+        s->masks_for = btcull::MaskKey{};          // (stays invalid if a launch fails)
         BT_HIP(bt_launch_block_masks(&P, n_blocks, s->d_block_masks.ptr, stream));
+        BT_HIP(bt_launch_block_order(s->d_block_masks.ptr, n_blocks, s->d_block_order.ptr, stream));
         s->masks_for = key;
     }
     P.block_masks = s->d_block_masks.ptr;
+    P.block_order = s->d_block_order.ptr;
     return 0;
 }
 
@@ -444,6 +450,7 @@ int render_common(bt_scene *s, uint64_t camera_ref, const bt_config *cfg, const 
     P.counters = s->d_counters + (size_t)s->last_slot * 16;
     BT_HIP(hipEventRecord(s->ev_start, stream));
     P.block_masks = nullptr;
+    P.block_order = nullptr;
     if (bt_launch_reads_masks(&P, plan.output)) {
         rcode = ensure_block_masks(s, P, plan.grid * (uint32_t)P.slices, stream);
         if (rcode) return rcode;
@@ -790,6 +797,28 @@ int bt_debug_block_masks_device(bt_scene *scene, uint64_t camera_ref, const bt_c
     (void)hipFree(d);
     if (e != hipSuccess) return fail(BT_ERR_DEVICE, hipGetErrorString(e));
     return n_blocks;
+}
+
+int bt_debug_block_order(const uint64_t *masks, uint32_t n_blocks, uint32_t *order_out, uint32_t *header_out) {
+    if (!masks || !order_out || !header_out || n_blocks == 0 || n_blocks > 0x7fffffffu) return fail(BT_ERR_INVALID_ARG, "bt_debug_block_order: null argument or no blocks");
+    btcull::block_order(masks, n_blocks, order_out, header_out);
+    return 0;
+}
+
+int bt_debug_block_order_device(const uint64_t *masks, uint32_t n_blocks, uint32_t *order_out, uint32_t *header_out) {
+    if (!masks || !order_out || !header_out || n_blocks == 0 || n_blocks > 0x7fffffffu) return fail(BT_ERR_INVALID_ARG, "bt_debug_block_order_device: null argument or no blocks");
+    uint64_t *d_masks = nullptr;
+    uint32_t *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_masks, sizeof(uint64_t) * (size_t)n_blocks);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(uint32_t) * ((size_t)n_blocks + BT_ORDER_HEADER));
+    if (e == hipSuccess) e = hipMemcpy(d_masks, masks, sizeof(uint64_t) * (size_t)n_blocks, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = bt_launch_block_order(d_masks, n_blocks, d_out, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(header_out, d_out, sizeof(uint32_t) * BT_ORDER_HEADER, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(order_out, d_out + BT_ORDER_HEADER, sizeof(uint32_t) * (size_t)n_blocks, hipMemcpyDeviceToHost);
+    if (d_masks) (void)hipFree(d_masks);
+    if (d_out) (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(BT_ERR_DEVICE, hipGetErrorString(e));
+    return 0;
 }
 
 int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,

@@ -291,9 +291,26 @@ template <class Rows> BT_HD uint64_t block_mask(const BtLaunch &P, Rows rows, ui
     return m;
 }
 
-// What block_mask() reads, besides the rows themselves: the key under which bt_api.cpp keeps a launch's masks on the scene
-// handle (compared with memcmp, so it is zeroed before it is filled).  WHOEVER MAKES block_geom, block_ref, block_extent,
-// primary_cone OR may_hit READ ANOTHER FIELD OF BtLaunch ADDS IT HERE.  `rows_generation` stands for the rows: bt_api.cpp
+// The order in which the render kernel's CULL builds take a launch's blocks: a stable partition of
+// 0 .. n_blocks - 1 -- first the blocks with a non-zero mask, ascending, then the blocks with a zero mask, ascending -- and
+// in front of it the two counts.  One buffer of BT_ORDER_HEADER + n_blocks words: [0] = n_live, [1] = n_empty, then the order.
+// This loop IS the definition; bt_block_order_kernel (bt_kernels.hip) must produce the same words.
+#define BT_ORDER_HEADER 2u
+BT_HD void block_order(const uint64_t *masks, uint32_t n_blocks, uint32_t *order, uint32_t *header) {
+    uint32_t n_live = 0;
+    for (uint32_t b = 0; b < n_blocks; ++b) n_live += masks[b] != 0ull ? 1u : 0u;
+    uint32_t live = 0, empty = n_live;
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        if (masks[b] != 0ull) order[live++] = b;
+        else order[empty++] = b;
+    }
+    header[0] = n_live;
+    header[1] = n_blocks - n_live;
+}
+
+// What block_mask() reads, besides the rows themselves: the key under which bt_api.cpp keeps a launch's masks, and the block
+// order made from them, on the scene handle (compared with memcmp, so it is zeroed before it is filled).  WHOEVER MAKES
+// block_geom, block_ref, block_extent, primary_cone OR may_hit READ ANOTHER FIELD OF BtLaunch ADDS IT HERE.  `rows_generation` stands for the rows: bt_api.cpp
 // bumps it wherever the table is uploaded.  `stream`: the masks are ordered behind work of that stream only.
 struct MaskKey {
     BtV3 cam_cx, cam_cy, cam_cz, cam_t;

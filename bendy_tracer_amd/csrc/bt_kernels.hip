@@ -28,9 +28,10 @@
 //     staged in LDS; the camera block of the launch parameters is read where it is used, not kept in SGPRs;
 //   * template flags select a build without rect code / without the volume march for scenes that have neither;
 //   * sphere-only launches without volumes: bt_block_mask_kernel (one thread per pixel block, double precision,
-//     bt_cull.hpp) writes which sphere rows each block's camera rays can reach, bt_api.cpp keeps the masks on the scene
-//     handle for as long as their inputs stay the same, and a workgroup of the render kernel whose mask is empty adds the
-//     background's value to its pixels and traces nothing -- one scalar load ahead of everything else;
+//     bt_cull.hpp) writes which sphere rows each block's camera rays can reach, bt_block_order_kernel lists the blocks that
+//     can reach any ahead of those that reach none, bt_api.cpp keeps both on the scene handle for as long as their inputs
+//     stay the same; the render kernel's first workgroups trace the listed blocks, the next few add the background's value
+//     to the pixels of the empty ones -- 256 pixels each, nothing traced -- and the rest return at once;
 //   * no MFMA: there is no dense contraction on this path.
 //
 // Round 3 removed what had lost every measurement of rounds 1 and 2 (the logs stay under profiles/): the lane-owns-pixel
@@ -231,15 +232,14 @@ BT_DEV void sum_blocks(const BtLaunch &P, const BlockGeom &g, uint32_t first, ui
     }
 }
 
-// A block whose mask is empty: every sample of it is one segment that misses, its value is sample_root's with the camera's
-// beta and L.  The workgroup adds that value T times to each pixel's running sum -- the additions sum_block() would perform on
-// the parked values, in the same order -- and traces nothing.
-template <int OUTPUT> BT_DEV void fill_empty_block(const BtLaunch &P) {
+// Blocks whose mask is empty: every sample of such a block is one segment that misses, its value is sample_root's with the
+// camera's beta and L.  A fill workgroup takes 256 >> LOG_PXB = `slices` of them, so that each of its 256 threads has one
+// pixel: thread t pixel t & (pxb - 1) of the empty block empties[first + (t >> LOG_PXB)], if the list reaches that far.  The
+// thread adds that value T times to the pixel's running sum -- the additions sum_block() would perform on the parked values,
+// in the same order -- and traces nothing.  One device atomic per workgroup: the segments of its blocks' pixels in the frame.
+template <int OUTPUT> BT_DEV void fill_empty_blocks(const BtLaunch &P, const uint32_t *empties, uint32_t first, uint32_t n_empty) {
     const BlockGeom G = block_geom(P);
-    const BlockRef B_own = block_ref(P, G, blockIdx.x);
     const uint32_t T = (uint32_t)P.samples * (uint32_t)(P.subsample_n * P.subsample_n);
-    uint32_t nx = 0, ny = 0;
-    block_extent(P, G, B_own, nx, ny);
     V3 value;
     if (OUTPUT == 0) {
         value = mk(0, 0, 0) + mk(1, 1, 1) * mk(P.root_color);      // L = L + beta * root_color, fresh L and beta
@@ -251,17 +251,41 @@ template <int OUTPUT> BT_DEV void fill_empty_block(const BtLaunch &P) {
         depth = fminf(fmaxf(depth, 0.0f), 1.0f);
         value = mk(depth, depth, depth);
     }
-    for (uint32_t q = threadIdx.x; q < G.pxb; q += blockDim.x) {
-        const PixelRef r = pixel_of(P, G, B_own, q);
-        if (!r.in_frame) continue;
-        float *o = out_of(P, P.out, B_own, r);
-        V3 sum = mk(o[0], o[1], o[2]);
-        for (uint32_t k = 0; k < T; ++k) sum = sum + value;
-        o[0] = sum.x;
-        o[1] = sum.y;
-        o[2] = sum.z;
+    const uint32_t e = first + (threadIdx.x >> G.LOG_PXB);
+    if (e < n_empty) {
+        const BlockRef B = block_ref(P, G, empties[e]);
+        const PixelRef r = pixel_of(P, G, B, threadIdx.x & (G.pxb - 1u));
+        if (r.in_frame) {
+            float *o = out_of(P, P.out, B, r);
+            V3 sum = mk(o[0], o[1], o[2]);
+            for (uint32_t k = 0; k < T; ++k) sum = sum + value;
+            o[0] = sum.x;
+            o[1] = sum.y;
+            o[2] = sum.z;
+        }
     }
-    if (P.counters && threadIdx.x == 0 && nx * ny != 0u) atomicAdd(&P.counters[0], (unsigned long long)(nx * ny) * T);
+    if (P.counters && threadIdx.x < 64u) {         // the first wave: lane j counts the pixels of the workgroup's j-th block
+        uint32_t pixels = 0;
+        if (threadIdx.x < G.NS && first + threadIdx.x < n_empty) {
+            const BlockRef B = block_ref(P, G, empties[first + threadIdx.x]);
+            uint32_t nx = 0, ny = 0;
+            block_extent(P, G, B, nx, ny);
+            pixels = nx * ny;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) pixels += __shfl_xor(pixels, off, 64);
+        if (threadIdx.x == 0 && pixels != 0u) atomicAdd(&P.counters[0], (unsigned long long)pixels * T);
+    }
+}
+
+// the inclusive prefix sum of `v` over the lanes of a wave
+BT_DEV uint32_t wave_scan_incl(uint32_t v, uint32_t lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(v, off, 64);
+        if ((int)lane >= off) v += o;
+    }
+    return v;
 }
 
 } // namespace
@@ -273,6 +297,60 @@ __global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t
     if (b >= n_blocks) return;
     typedef const __attribute__((address_space(4))) BtSphereRow RowK;
     masks[b] = btcull::block_mask(P, (RowK *)P.sphere_rows, b);
+}
+
+// The blocks of a launch in the order the CULL builds of the render kernel take them: out = {n_live, n_empty, order[n_blocks]},
+// word for word what btcull::block_order (bt_cull.hpp) writes.  ONE workgroup, launched behind bt_block_mask_kernel on the same
+// stream (stream order is all the ordering there is): it counts the non-zero masks, then scans them in chunks of
+// BT_ORDER_CHUNK -- four consecutive masks per thread, a wave scan, the 16 wave totals through LDS (two sets, alternating:
+// one barrier per chunk).  Once per camera, like the masks.
+#define BT_ORDER_THREADS 1024
+#define BT_ORDER_PER_THREAD 4
+#define BT_ORDER_CHUNK (BT_ORDER_THREADS * BT_ORDER_PER_THREAD)
+__global__ __launch_bounds__(BT_ORDER_THREADS) void bt_block_order_kernel(const unsigned long long *masks, uint32_t n_blocks, uint32_t *out) {
+    constexpr uint32_t NW = BT_ORDER_THREADS / 64;
+    __shared__ uint32_t s_wave[2][NW];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    uint32_t mine = 0;
+    for (uint32_t b = t; b < n_blocks; b += BT_ORDER_THREADS) mine += masks[b] != 0ull ? 1u : 0u;
+    uint32_t incl = wave_scan_incl(mine, lane);
+    if (lane == 63u) s_wave[0][wave] = incl;
+    __syncthreads();
+    uint32_t n_live = 0;
+    for (uint32_t w = 0; w < NW; ++w) n_live += s_wave[0][w];
+    if (t == 0) {
+        out[0] = n_live;
+        out[1] = n_blocks - n_live;
+    }
+    uint32_t *order = out + BT_ORDER_HEADER;
+    uint32_t live_base = 0, set = 1;               // live blocks ahead of this chunk
+    for (uint32_t c0 = 0; c0 < n_blocks; c0 += BT_ORDER_CHUNK, set ^= 1u) {
+        const uint32_t b0 = c0 + t * BT_ORDER_PER_THREAD;
+        bool live[BT_ORDER_PER_THREAD];
+        mine = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < BT_ORDER_PER_THREAD; ++j) {
+            live[j] = b0 + j < n_blocks && masks[b0 + j] != 0ull;
+            mine += live[j] ? 1u : 0u;
+        }
+        incl = wave_scan_incl(mine, lane);
+        if (lane == 63u) s_wave[set][wave] = incl;
+        __syncthreads();
+        uint32_t before = live_base + incl - mine, total = 0;      // live blocks ahead of b0
+        for (uint32_t w = 0; w < NW; ++w) {
+            const uint32_t v = s_wave[set][w];
+            total += v;
+            if (w < wave) before += v;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < BT_ORDER_PER_THREAD; ++j) {
+            const uint32_t b = b0 + j;
+            if (b >= n_blocks) break;
+            if (live[j]) order[before++] = b;
+            else order[n_live + (b - before)] = b;                 // b - before: empty blocks ahead of b
+        }
+        live_base += total;
+    }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -311,9 +389,10 @@ __global__ __launch_bounds__(256) void bt_block_mask_kernel(BtLaunch P, uint32_t
 template <int OUTPUT, bool LENS, bool RECTS, bool VOLS, bool PACKED>
 __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER_SIMD_GUIDED_RECTS : LENS ? BT_WAVES_PER_SIMD_LENS : (RECTS ? BT_WAVES_PER_SIMD_RECTS : (VOLS ? BT_WAVES_PER_SIMD_VOLS : BT_WAVES_PER_SIMD))) void bt_render_kernel(BtLaunch P) {
     // ---- a block whose camera rays provably reach no sphere (sphere-only builds without volumes) ----
-    // bt_block_mask_kernel has written which sphere rows the block's camera rays can reach: one wave-uniform (scalar) load,
-    // ahead of the LDS staging and its barrier, which an empty block does not need.  The Normal output's miss value depends
-    // on the direction and is not shortcut.
+    // bt_block_mask_kernel has written which sphere rows each block's camera rays can reach and bt_block_order_kernel has
+    // listed the blocks that reach any ahead of those that reach none.  The kernel reads the list, not the masks: two
+    // wave-uniform (scalar) loads ahead of the LDS staging and its barrier, which the empty blocks do not need (see `bid`
+    // below).  The Normal output's miss value depends on the direction and is not shortcut.
     constexpr bool GUIDED = OUTPUT == 4;   // every statement of the guided builds sits behind this constant
     constexpr bool ADAPT = OUTPUT == 5;    // ... and every statement of the adaptive builds behind this one
     constexpr bool AOV = OUTPUT != 0 && !ADAPT;    // the build keeps a path's first hit (the adaptive builds are Full builds)
@@ -330,18 +409,30 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
         const uint32_t slot = blockIdx.x >> (uint32_t)__builtin_ctz((uint32_t)C->slices);
         if (((ActiveK *)C->tile_active)[slot] == 0u) return;
     }
-    if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE)
-        typedef const __attribute__((address_space(4))) unsigned long long MaskK;
-        if (((MaskK *)P.block_masks)[blockIdx.x] == 0ull) {
-            // The empty path reads the launch parameters through a pointer the compiler cannot see through (as the camera
-            // event below does): sharing block_ref() and the like with the code after it kept their inputs in SGPRs across
-            // this branch, and the loop paid with 18 more spill reloads per iteration (profiles/r10).
-            typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
-            BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(C));
-            fill_empty_block<OUTPUT>(*(const BtLaunch *)C);
+    // Which block this workgroup traces.  The CULL builds take the launch's blocks in bt_block_order_kernel's order: workgroup w <
+    // n_live traces the w-th block with a non-zero mask (so the sky at the top of a frame does not hold the first half of the
+    // grid); the next ceil(n_empty / slices) workgroups fill `slices` empty blocks each, 256 pixels for 256 threads; the rest
+    // of the grid returns at once -- it is dispatched last, while the traced workgroups drain.  Nothing depends on the order
+    // in which the hardware starts workgroups.
+    uint32_t bid = blockIdx.x;
+    if (CULL && P.max_bounces >= 0) {              // (max_bounces < 0 ends every path before its first TRACE: plain launch order)
+        // Header, order and everything the fill reads come through a pointer the compiler cannot see through (as the camera
+        // event below does): sharing block_ref() and the like with the code after it kept their inputs in SGPRs across
+        // this branch, and the loop paid with 18 more spill reloads per iteration (profiles/r10).
+        typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
+        typedef const __attribute__((address_space(4))) uint32_t OrderK;
+        BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(C));
+        OrderK *ord = (OrderK *)C->block_order;
+        const uint32_t n_live = ord[0];
+        if (blockIdx.x >= n_live) {
+            const uint32_t n_empty = ord[1], log_ns = (uint32_t)__builtin_ctz((uint32_t)C->slices);
+            const uint32_t fw = blockIdx.x - n_live;                          // which fill workgroup
+            if (fw >= (n_empty + (1u << log_ns) - 1u) >> log_ns) return;
+            fill_empty_blocks<OUTPUT>(*(const BtLaunch *)C, (const uint32_t *)C->block_order + BT_ORDER_HEADER + n_live, fw << log_ns, n_empty);
             return;
         }
+        bid = ord[BT_ORDER_HEADER + blockIdx.x];
     }
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ uint32_t s_waves_done;      // block queue: waves of this workgroup that have parked all their samples
@@ -419,17 +510,17 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
     const uint32_t nn = (uint32_t)(P.subsample_n * P.subsample_n);
     const uint32_t T = (uint32_t)P.samples * nn;       // samples per pixel in this launch
     const uint32_t sample0 = P.sample_base * nn;
-    // block queue: this workgroup's one block (launch order = blockIdx.x) -- or, in a packed launch (wg_blocks > 1: gridDim.x
+    // block queue: this workgroup's one block (`bid` above) -- or, in a packed launch (wg_blocks > 1: gridDim.x
     // workgroups for the launch's blocks), the blocks blockIdx.x, blockIdx.x + gridDim.x, ... behind ONE queue: item
     // i = ((j << log_rows | k) << LOG_PXB) + pixel for sample k of the workgroup's j-th block (rows k >= T are holes: T is
     // padded to a power of two so that neither j nor k costs a division)
     constexpr bool packed = PACKED;
     const uint32_t my_blocks = packed ? P.wg_blocks - (blockIdx.x < P.wg_blocks_rem ? 0u : 1u) : 1u;
     const uint32_t n_items = packed ? (my_blocks << (P.log_rows + LOG_PXB)) : pxb * T;      // work items of this workgroup
-    const BlockRef B_own = block_ref(P, G, blockIdx.x);
+    const BlockRef B_own = block_ref(P, G, bid);
     // where this workgroup parks: every workgroup of a packed launch has room for wg_blocks blocks
     auto park = [&]() -> Parked * {
-        return (Parked *)P.scratch + (size_t)blockIdx.x * (packed ? (size_t)P.wg_blocks << (P.log_rows + LOG_PXB) : (size_t)n_items);
+        return (Parked *)P.scratch + (size_t)bid * (packed ? (size_t)P.wg_blocks << (P.log_rows + LOG_PXB) : (size_t)n_items);
     };
 
     // the lane's current work item: pixel_index keys the Philox counter; park_i = the item's number i = k * pxb + pixel in
@@ -468,7 +559,7 @@ __global__ __launch_bounds__(256, (OUTPUT == 4 && RECTS && !VOLS) ? BT_WAVES_PER
         typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
         BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(C));
-        const size_t at = (size_t)blockIdx.x * (packed ? (size_t)P.wg_blocks << (P.log_rows + LOG_PXB) : (size_t)n_items) + park_i;
+        const size_t at = (size_t)bid * (packed ? (size_t)P.wg_blocks << (P.log_rows + LOG_PXB) : (size_t)n_items) + park_i;
         if (C->guide_out[0]) ((Parked *)C->guide_scratch[0])[at] = Parked{albedo.x, albedo.y, albedo.z};
         if (C->guide_out[1]) ((Parked *)C->guide_scratch[1])[at] = Parked{nrm.x, nrm.y, nrm.z};
         if (C->guide_out[2]) {
@@ -1006,15 +1097,15 @@ queue_empty:;
                 typedef const __attribute__((address_space(4))) BtLaunch BtLaunchK;
                 BtLaunchK *C = (BtLaunchK *)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(C));
-                sum_block<Parked, true>(P, G, blockIdx.x, T, park(), lane, P.out, C->moment);
+                sum_block<Parked, true>(P, G, bid, T, park(), lane, P.out, C->moment);
             } else {
-                sum_block(P, G, blockIdx.x, T, park(), lane, P.out);
+                sum_block(P, G, bid, T, park(), lane, P.out);
             }
             if (GUIDED) {                                                 // each guide's plane, the same additions into its own frame
-                const size_t at = (size_t)blockIdx.x * (size_t)n_items;
-                if (P.guide_out[0]) sum_block(P, G, blockIdx.x, T, (const Parked *)P.guide_scratch[0] + at, lane, P.guide_out[0]);
-                if (P.guide_out[1]) sum_block(P, G, blockIdx.x, T, (const Parked *)P.guide_scratch[1] + at, lane, P.guide_out[1]);
-                if (P.guide_out[2]) sum_block(P, G, blockIdx.x, T, (const Parked1 *)P.guide_scratch[2] + at, lane, P.guide_out[2]);
+                const size_t at = (size_t)bid * (size_t)n_items;
+                if (P.guide_out[0]) sum_block(P, G, bid, T, (const Parked *)P.guide_scratch[0] + at, lane, P.guide_out[0]);
+                if (P.guide_out[1]) sum_block(P, G, bid, T, (const Parked *)P.guide_scratch[1] + at, lane, P.guide_out[1]);
+                if (P.guide_out[2]) sum_block(P, G, bid, T, (const Parked1 *)P.guide_scratch[2] + at, lane, P.guide_out[2]);
             }
         }
     }
@@ -1075,7 +1166,7 @@ __global__ __launch_bounds__(256) void bt_preview_kernel(const float4 *rgba, uin
 extern "C" void bt_primary_masks_host(const BtLaunch *P, const BtSphereRow *rows, uint32_t n_blocks, uint64_t *out) {
     for (uint32_t b = 0; b < n_blocks; ++b) out[b] = btcull::block_mask(*P, rows, b);
 }
-// Does a launch of `P` run a build that reads BtLaunch::block_masks (the kernel's CULL)?
+// Does a launch of `P` run a build that reads BtLaunch::block_masks / block_order (the kernel's CULL)?
 extern "C" int bt_launch_reads_masks(const BtLaunch *P, int output) {
     return !P->any_rects && !P->any_volumes && !P->lens_on && P->wg_blocks <= 1 && output != 2 && output != 4 && output != 5 && P->max_bounces >= 0;
 }
@@ -1093,12 +1184,19 @@ extern "C" hipError_t bt_launch_block_masks(const BtLaunch *P, uint32_t n_blocks
                        (unsigned long long *)masks);
     return hipGetLastError();
 }
+// btcull::block_order's words ({n_live, n_empty, order[n_blocks]}) on the device, from the masks bt_launch_block_masks has written on the same stream
+extern "C" hipError_t bt_launch_block_order(const uint64_t *masks, uint32_t n_blocks, uint32_t *out, hipStream_t stream) {
+    if (n_blocks == 0 || !masks || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bt_block_order_kernel, dim3(1), dim3(BT_ORDER_THREADS), 0, stream, (const unsigned long long *)masks,
+                       n_blocks, out);
+    return hipGetLastError();
+}
 extern "C" hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned grid, size_t lds_bytes,
                                        hipStream_t stream) {
     // grid = tiles to render; a tile is P->slices workgroups (see the mapping in the kernel)
     const bool packed = P->wg_blocks > 1;          // bt_api.cpp packs launches without the lens only
     if (packed && P->lens_on) return hipErrorInvalidValue;
-    if (bt_launch_reads_masks(P, output) && !P->block_masks) return hipErrorInvalidValue;   // no masks, no launch
+    if (bt_launch_reads_masks(P, output) && (!P->block_masks || !P->block_order)) return hipErrorInvalidValue;   // no masks or no order, no launch
     dim3 g(packed ? P->n_workgroups : grid * (unsigned)P->slices), b(256);
     // scene classes: bit 0 = some sphere carries a volume (volume.json, cloud.json), bit 1 = rects / cuboids present
     // (the Cornell boxes); scene.json is class 0

@@ -240,7 +240,9 @@ struct BtLaunch {
     uint32_t log_rows, row_mask;      // packed: a block's T = samples * n^2 samples are padded to 2^log_rows rows in the queue and in
                                       // scratch, row_mask = 2^log_rows - 1; not packed: row_mask = 0xffffffff
     // Sphere-only launches without volumes, lens and packing (bt_kernels.hip CULL): per block of the launch, in launch order,
-    // the sphere rows its camera rays can reach (bt_cull.hpp block_mask, written by bt_block_mask_kernel); else null
+    // the sphere rows its camera rays can reach (bt_cull.hpp block_mask, written by bt_block_mask_kernel); else null.  The
+    // render kernel itself dereferences `block_order` below, which is made from these masks, and not the masks; the pointer
+    // stays in the launch as the proof that the order it reads belongs to masks of this launch (bt_launch_render wants both)
     const uint64_t *block_masks;
     // Guided render EXTENSION (not in the reference; bt_render_guided_device, the OUTPUT == 4 builds of bt_kernels.hip): the
     // frames the first-hit albedo / normal / depth values of the colour paths are added to, [0] albedo, [1] normal, [2] depth
@@ -255,4 +257,8 @@ struct BtLaunch {
     // fields for the same reason: no other build reads them.
     const uint32_t *tile_active;
     float *moment;
+    // The CULL builds again: the order in which the launch's workgroups take its blocks (bt_cull.hpp block_order, written by
+    // bt_block_order_kernel next to the masks): [0] = n_live, [1] = n_empty, then the blocks with a non-zero mask followed by
+    // those with a zero mask; null wherever block_masks is null.  Appended behind everything else: no kernarg offset moves.
+    const uint32_t *block_order;
 };

@@ -186,6 +186,12 @@ int bt_debug_set_object(bt_scene *scene, uint64_t object_ref, const float *trans
 int bt_debug_block_masks_device(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
                                 uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world,
                                 uint64_t *masks, uint32_t cap);
+/* For tests: the order in which a launch takes its blocks, from their masks (bt_debug_primary_mask's): order_out[n_blocks] =
+ * the indices of the non-zero masks, ascending, then those of the zero masks, ascending; header_out[2] = the two counts.
+ * Computed on the host by the function that defines the result.  Returns 0. */
+int bt_debug_block_order(const uint64_t *masks, uint32_t n_blocks, uint32_t *order_out, uint32_t *header_out);
+/* For tests: the same, written by the kernel the renders get their order from, on the current device, and copied back. */
+int bt_debug_block_order_device(const uint64_t *masks, uint32_t n_blocks, uint32_t *order_out, uint32_t *header_out);
 /* For tests: the bytes of the key under which a handle keeps such a launch's masks between renders (stream = NULL, no
  * device address): any input the masks depend on must change them.  Writes up to `cap` bytes, returns the key's size. */
 int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
