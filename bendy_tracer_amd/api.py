@@ -234,7 +234,7 @@ EXPORTS = [
     "bt_comm_unique_id", "bt_comm_init", "bt_comm_free", "bt_comm_rank", "bt_comm_world", "bt_allgather_shards_device",
     "bt_exchange_frame_device", "bt_scene_last_stats", "bt_tuning_default", "bt_scene_set_tuning", "bt_scene_get_tuning", "bt_scene_default", "bt_scene_to_json", "bt_scene_save", "bt_write_png",
     "bt_scene_trim", "bt_denoise_params_default", "bt_denoiser_new", "bt_denoiser_free", "bt_denoise_device",
-    "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_block_order", "bt_debug_block_order_device", "bt_debug_set_object",
+    "bt_denoise", "bt_debug_primary_mask", "bt_debug_block_masks_device", "bt_debug_mask_key", "bt_debug_block_order", "bt_debug_block_order_device", "bt_debug_philox_device", "bt_debug_set_object",
     "bt_debug_plan_launch",
     "bt_render_guided_device", "bt_adaptive_params_default", "bt_adaptive_new", "bt_adaptive_free", "bt_adaptive_reset",
     "bt_render_adaptive_device", "bt_adaptive_poll", "bt_adaptive_counts", "bt_adaptive_errors", "bt_debug_adaptive_moments",
@@ -301,6 +301,7 @@ def _load():
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32]
     L.bt_debug_block_order.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.bt_debug_block_order_device.argtypes = L.bt_debug_block_order.argtypes
+    L.bt_debug_philox_device.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
     L.bt_debug_plan_launch.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
                                        C.POINTER(Stats)]
@@ -798,6 +799,20 @@ class Tracer:
         _check(fn(m.ctypes.data_as(C.POINTER(C.c_uint64)), m.size, order.ctypes.data_as(C.POINTER(C.c_uint32)),
                   header.ctypes.data_as(C.POINTER(C.c_uint32))))
         return order, (int(header[0]), int(header[1]))
+
+    @staticmethod
+    def philox_device(counters, keys):
+        """bt_debug_philox_device (tests): the device's Philox4x32-10, in the form the sphere-only render builds run it, over
+        counters [n, 4] and keys [n, 2] (uint32); returns the words [n, 4]."""
+        c = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 4)
+        k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1, 2)
+        if c.shape[0] != k.shape[0]:
+            raise ValueError("as many keys as counters")
+        pairs = np.ascontiguousarray(np.concatenate([c, k], axis=1))
+        out = np.zeros((c.shape[0], 4), dtype=np.uint32)
+        _check(lib.bt_debug_philox_device(pairs.ctypes.data_as(C.POINTER(C.c_uint32)), c.shape[0],
+                                          out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     def mask_key(self, scene: Scene, camera: int, config: RenderConfig, width, height, slices, rank=0, world=1) -> bytes:
         """bt_debug_mask_key (tests): the key under which the handle would keep these masks between renders."""

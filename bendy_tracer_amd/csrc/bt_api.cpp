@@ -821,6 +821,20 @@ int bt_debug_block_order_device(const uint64_t *masks, uint32_t n_blocks, uint32
     return 0;
 }
 
+int bt_debug_philox_device(const uint32_t *pairs, uint32_t n, uint32_t *out) {
+    if (!pairs || !out || n == 0 || n > (1u << 24)) return fail(BT_ERR_INVALID_ARG, "bt_debug_philox_device: null argument, no pairs or more than 2^24");
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_in, sizeof(uint32_t) * 6 * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(uint32_t) * 4 * (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(d_in, pairs, sizeof(uint32_t) * 6 * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = bt_launch_philox_test(d_in, n, d_out, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(uint32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(BT_ERR_DEVICE, hipGetErrorString(e));
+    return 0;
+}
+
 int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
                       uint32_t width, uint32_t height, uint32_t slices, uint32_t rank, uint32_t world, uint8_t *out,
                       uint32_t cap) {

@@ -140,6 +140,15 @@ BT_DEV U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0
     U4 r; r.x = c0; r.y = c1; r.z = c2; r.w = c3;
     return r;
 }
+// The same ten rounds for a wave-uniform key that the compiler must not expand ahead of the call (the sphere-only builds
+// without volumes).  Left to itself it hoists the 18 round keys (seed + i * constant) out of the render loop
+// into SGPRs that stay live across it, which costs these builds their SGPR granule and other values their registers.  Behind
+// the opaque copy the nine adds per half run on the scalar unit in every call (it has the time: profiles/r15) and the
+// keys die with the call.  Additions are mod 2^32 either way: the same words.  k0 and k1 must be wave-uniform.
+BT_DEV U4 philox_ukeys(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    asm volatile("" : "+s"(k0), "+s"(k1));
+    return philox(c0, c1, c2, c3, k0, k1);
+}
 BT_DEV float u23(uint32_t x) { return __uint_as_float((x >> 9) | 0x3F800000u) - 1.0f; }
 BT_DEV float u24(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }
 BT_DEV bool bernoulli(uint32_t x, float p) { return u24(x) < p; }

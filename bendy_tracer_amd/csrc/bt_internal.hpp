@@ -48,6 +48,7 @@ int bt_mask_cache_enabled(void);
 hipError_t bt_launch_block_masks(const BtLaunch *P, uint32_t n_blocks, uint64_t *masks, hipStream_t stream);
 // out: BT_ORDER_HEADER + n_blocks words (bt_cull.hpp block_order)
 hipError_t bt_launch_block_order(const uint64_t *masks, uint32_t n_blocks, uint32_t *out, hipStream_t stream);
+hipError_t bt_launch_philox_test(const uint32_t *pairs, uint32_t n, uint32_t *out, hipStream_t stream);
 hipError_t bt_launch_preview(const float *rgba, uint8_t *out, uint32_t n, uint32_t samples, int color_space, hipStream_t stream);
 // bt_adapt.hip
 hipError_t bt_launch_adapt_update(const float *rgba, const float *moment, uint32_t *count, uint32_t *active, float *error,

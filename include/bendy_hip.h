@@ -192,6 +192,11 @@ int bt_debug_block_masks_device(bt_scene *scene, uint64_t camera_ref, const bt_c
 int bt_debug_block_order(const uint64_t *masks, uint32_t n_blocks, uint32_t *order_out, uint32_t *header_out);
 /* For tests: the same, written by the kernel the renders get their order from, on the current device, and copied back. */
 int bt_debug_block_order_device(const uint64_t *masks, uint32_t n_blocks, uint32_t *order_out, uint32_t *header_out);
+/* For tests: the device's Philox4x32-10 in the form the sphere-only render builds run it (wave-uniform key)
+ * on the current device: pairs[6 * i ...] = counter words c0 .. c3, key words k0, k1 of pair i; out[4 * i ...] = its four
+ * words.  Each wave takes 64 pairs and goes through their keys one at a time, so that the key is wave-uniform as a launch's
+ * seed is.  Returns 0. */
+int bt_debug_philox_device(const uint32_t *pairs, uint32_t n, uint32_t *out);
 /* For tests: the bytes of the key under which a handle keeps such a launch's masks between renders (stream = NULL, no
  * device address): any input the masks depend on must change them.  Writes up to `cap` bytes, returns the key's size. */
 int bt_debug_mask_key(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render,
