@@ -221,6 +221,24 @@ class CompareStats(C.Structure):  # include/bendy_hip.h `bt_compare_stats` (exte
         return "CompareStats(" + ", ".join(f"{k}={getattr(self, k)!r}" for k, _ in self._fields_) + ")"
 
 
+# include/bendy_hip.h `bt_ray` (32 B) and `bt_hit` (64 B) (extension): numpy views of the query's buffers
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")])
+HIT_DTYPE = np.dtype([("position", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("face", "<i4"), ("object_ref", "<u8"),
+                      ("material_ref", "<u8"), ("volume_ref", "<u8"), ("prim", "<i4"), ("reserved", "<u4")])
+FACE_MISS, FACE_FRONT, FACE_BACK, FACE_VOLUME_FRONT, FACE_VOLUME_BACK = -1, 0, 1, 3, 4
+NO_REF = 0xFFFFFFFFFFFFFFFF
+
+
+class _CRay(C.Structure):  # include/bendy_hip.h `bt_ray` (extension)
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class _CHit(C.Structure):  # include/bendy_hip.h `bt_hit` (extension)
+    _fields_ = [("position", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("face", C.c_int32),
+                ("object_ref", C.c_uint64), ("material_ref", C.c_uint64), ("volume_ref", C.c_uint64), ("prim", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
 class _CLens(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("rs", C.c_float), ("step", C.c_float), ("radius", C.c_float),
                 ("max_steps", C.c_uint32)]
@@ -253,6 +271,7 @@ EXPORTS = [
     "bt_debug_upscale_weights", "bt_debug_upscale_plane", "bt_debug_upscale_host",
     "bt_compare_params_default", "bt_compare_new", "bt_compare_free", "bt_compare_device", "bt_compare_poll", "bt_compare_tail",
     "bt_compare_map_device", "bt_debug_compare_plane", "bt_debug_compare_host", "bt_read_pfm",
+    "bt_query_rays_device", "bt_view_rays_device", "bt_scene_pick", "bt_scene_set_camera_focus",
 ]
 
 
@@ -417,6 +436,11 @@ def _load():
     L.bt_debug_compare_host.argtypes = [fp, C.c_uint32, fp, C.c_uint32, C.c_uint32, C.c_uint32, cpp, C.POINTER(CompareStats), fp, dp, dp,
                                         C.c_uint32, dp, dp, fp]
     L.bt_read_pfm.argtypes = [C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.bt_query_rays_device.argtypes = [vp, vp, C.c_uint32, vp, vp]
+    L.bt_view_rays_device.argtypes = [C.POINTER(View), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    L.bt_scene_pick.argtypes = [vp, C.c_uint64, C.POINTER(_CConfig), C.POINTER(_CRenderConfig), C.c_uint32, C.c_uint32, C.c_uint32,
+                                C.c_uint32, C.POINTER(_CHit), fp]
+    L.bt_scene_set_camera_focus.argtypes = [vp, C.c_uint64, C.c_int, C.c_float]
     return L
 
 
@@ -516,6 +540,41 @@ class Scene:
         if len(m) != 12:
             raise BendyError(-1, f"to_world needs 12 floats, not {len(m)}")
         _check(lib.bt_scene_set_camera_pose(self._h, camera, (C.c_float * 12)(*m)))
+
+    def set_camera_focus(self, camera, focus):
+        """EXTENSION, not in the reference (bt_scene_set_camera_focus): replaces the camera's focus distance in place on this
+        handle; None clears it (no depth of field).  The JSON that `save` / `to_json` write is not updated."""
+        _check(lib.bt_scene_set_camera_focus(self._h, camera, 0 if focus is None else 1, 0.0 if focus is None else float(focus)))
+
+    def query(self, rays, out=None):
+        """EXTENSION, not in the reference (bt_query_rays_device): the closest hit of each ray -- `try_hit`
+        (tracer/mod.rs:389-402) with the clip taken from the ray.  `rays`: a contiguous CUDA float32 tensor [n, 8], a row being
+        a `bt_ray` (origin, tmin, dir, tmax; `dir` is used as given).  Returns a uint8 tensor [n, 64] of `bt_hit` records on the
+        same device, enqueued on the current stream and not synchronised; `hits_numpy` views it as HIT_DTYPE."""
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous()):
+            raise BendyError(-1, "rays must be a contiguous CUDA float32 tensor [n, 8]")
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, 64), dtype=torch.uint8, device=rays.device)
+        elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n, 64) and out.is_contiguous()):
+            raise BendyError(-1, f"out must be a contiguous CUDA uint8 tensor [{n}, 64]")
+        if n:
+            _check(lib.bt_query_rays_device(self._h, rays.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        return out
+
+    def pick(self, camera, config: "Config", render: "RenderConfig", width, height, x, y):
+        """EXTENSION, not in the reference (bt_scene_pick; synchronises): what the ray through the centre of pixel (x, y) hits --
+        None, or a dict of the `bt_hit` fields plus `focus`, the camera focus that puts the hit point in the focal plane."""
+        c, r = _c_configs(config, render, 0)
+        hit, focus = _CHit(), C.c_float(0.0)
+        if _check(lib.bt_scene_pick(self._h, camera, C.byref(c), C.byref(r), width, height, x, y, C.byref(hit), C.byref(focus))) == 0:
+            return None
+        return {"position": [float(v) for v in hit.position], "t": float(hit.t), "normal": [float(v) for v in hit.normal],
+                "face": int(hit.face), "object_ref": int(hit.object_ref), "material_ref": int(hit.material_ref),
+                "volume_ref": None if hit.volume_ref == NO_REF else int(hit.volume_ref), "prim": int(hit.prim),
+                "focus": float(focus.value)}
 
     def set_lens(self, centre, rs, step, radius, max_steps=4096):
         """EXTENSION, not in the reference (include/bendy_hip.h `bt_lens`): bend rays around a point mass."""
@@ -1813,6 +1872,24 @@ def compare_host(test, reference, test_samples=1, reference_samples=1, tail=(), 
                                      C.byref(st), E.ctypes.data_as(fp), V.ctypes.data_as(dp), S.ctypes.data_as(dp), len(fr),
                                      fr.ctypes.data_as(dp), shares.ctypes.data_as(dp), thresholds.ctypes.data_as(fp)))
     return st, E, V, S, [(float(s), float(t)) for s, t in zip(shares, thresholds)]
+
+
+def hits_numpy(hits):
+    """The uint8 [n, 64] tensor of `Scene.query` as a numpy array of HIT_DTYPE records (synchronises; copies to the host)."""
+    return hits.cpu().numpy().reshape(-1).view(HIT_DTYPE)
+
+
+def view_rays(view: View, x0, y0, w, h, out=None):
+    """EXTENSION, not in the reference (bt_view_rays_device): the rays through the footprint centres of the pixels
+    of a rectangle of `view`'s frame, row-major -- a CUDA float32 tensor [w * h, 8] that `Scene.query` takes.  Enqueued on the
+    current stream, not synchronised."""
+    import torch
+    if out is None:
+        out = torch.empty((max(int(w) * int(h), 0), 8), dtype=torch.float32, device="cuda")
+    elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (w * h, 8) and out.is_contiguous()):
+        raise BendyError(-1, f"out must be a contiguous CUDA float32 tensor [{w * h}, 8]")
+    _check(lib.bt_view_rays_device(C.byref(view), x0, y0, w, h, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return out
 
 
 def read_pfm(path):

@@ -43,6 +43,10 @@
 // must have the shown frame's size: MSE, relMSE, PSNR, SSIM, the largest difference, and the share of the error carried by the worst
 // F (0.01 unless told) of the pixels.  The figures are printed and --stats-json gains a `compare` object; --compare-map saves the
 // error plane in false colour, white at S (1 unless told).  It changes no output.
+// --pick X,Y and --autofocus X,Y (extension too; bt_scene_pick, bt_scene_set_camera_focus): what the ray through the centre of
+// pixel (X, Y) of the --width x --height frame hits, before the first render.  --pick prints one JSON line {"pick": {...}} to
+// stdout ({"pick": null} for a miss) and --stats-json gains the same object; --autofocus sets the camera's focus to the pick's,
+// so that the hit point lies in the focal plane of every render that follows (a miss is an error).  Not with --lens or --shard.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -145,6 +149,8 @@ struct Args {
     std::string compare, compare_map;                    // --compare TRUTH.pfm, --compare-map PATH.png
     double compare_tail = -1.0;                          // < 0: not given (0.01)
     float compare_map_scale = -1.0f;                     // < 0: not given (1)
+    bool pick = false, autofocus = false;                // --pick X,Y, --autofocus X,Y
+    unsigned pick_x = 0, pick_y = 0, autofocus_x = 0, autofocus_y = 0;
     long upscale_guide_samples = -1;                      // -1: not given (1)
 };
 
@@ -188,7 +194,10 @@ void usage() {
                  "                             full only, not with --shard, --lens, --resample, --denoise, --adaptive or --temporal)\n"
                  "       [--compare TRUTH.pfm] [--compare-tail 0.01] [--compare-map PATH.png] [--compare-map-scale 1]\n"
                  "                            (extension: MSE, relMSE, PSNR, SSIM and the tail share of the frame --hdr would write\n"
-                 "                             against a PFM of the same size; --output full only, not with --shard)\n");
+                 "                             against a PFM of the same size; --output full only, not with --shard)\n"
+                 "       [--pick X,Y] [--autofocus X,Y]\n"
+                 "                            (extension: what the ray through pixel (X, Y) hits, as one JSON line; the camera focus\n"
+                 "                             that puts it in the focal plane, set before the first render; not with --lens, --shard)\n");
 }
 
 Args parse(int argc, char **argv) {
@@ -356,6 +365,14 @@ Args parse(int argc, char **argv) {
             if (spec.empty() || *end != 0 || a.upscale_guide_samples < 1 || a.upscale_guide_samples > 0xffff)
                 die("--upscale-guide-samples expects a count in 1 .. 65535");
         }
+        else if (k == "--pick" || k == "--autofocus") {
+            const std::string spec = val();
+            unsigned x = 0, y = 0;
+            char tail = 0;
+            if (std::sscanf(spec.c_str(), "%u,%u%c", &x, &y, &tail) != 2 || spec[0] == '-') die(k + " expects X,Y");
+            if (k == "--pick") { a.pick = true; a.pick_x = x; a.pick_y = y; }
+            else { a.autofocus = true; a.autofocus_x = x; a.autofocus_y = y; }
+        }
         else if (k == "--compare") a.compare = val();
         else if (k == "--compare-map") a.compare_map = val();
         else if (k == "--compare-tail") {
@@ -421,6 +438,15 @@ Args parse(int argc, char **argv) {
     if (a.upscale && a.temporal) die("--upscale does not apply to a --temporal run");
     if (a.upscale && (a.upscale_width < a.width || a.upscale_height < a.height))
         die("--upscale must not be smaller than --width x --height on either axis: --resample reduces");
+    for (int which = 0; which < 2; ++which) {
+        if (!(which ? a.autofocus : a.pick)) continue;
+        const std::string name = which ? "--autofocus" : "--pick";
+        const unsigned x = which ? a.autofocus_x : a.pick_x, y = which ? a.autofocus_y : a.pick_y;
+        if (x >= a.width || y >= a.height)
+            die(name + ": pixel (" + std::to_string(x) + ", " + std::to_string(y) + ") is outside the " + std::to_string(a.width) + "x" + std::to_string(a.height) + " frame");
+        if (a.has_lens) die(name + " sends a straight ray: not with --lens");
+        if (a.shard_world > 1) die(name + " does not apply to a --shard run");
+    }
     if (a.compare.empty() && (a.compare_tail >= 0.0 || !a.compare_map.empty() || a.compare_map_scale >= 0.0f))
         die("--compare-tail, --compare-map and --compare-map-scale need --compare");
     if (a.compare_map.empty() && a.compare_map_scale >= 0.0f) die("--compare-map-scale needs --compare-map");
@@ -489,6 +515,37 @@ int main(int argc, char **argv) {
     bt_render_config_default(&rc);
     rc.subsample_n = args.subsample <= 1 ? 0 : args.subsample;   // main.rs:234-237
     const unsigned nn = rc.subsample_n ? rc.subsample_n * rc.subsample_n : 1;
+
+    // --pick / --autofocus (extension): before anything is rendered
+    std::string pick_json;
+    if (args.pick) {
+        bt_hit hit{};
+        float focus = 0.0f;
+        const int found = bt_scene_pick(scene, camera, &cfg, &rc, args.width, args.height, args.pick_x, args.pick_y, &hit, &focus);
+        check(found, "bt_scene_pick");
+        char pj[640] = "\"pick\": null";
+        if (found) {
+            char vol[32] = "null";
+            if (hit.volume_ref != UINT64_MAX) std::snprintf(vol, sizeof vol, "%llu", (unsigned long long)hit.volume_ref);
+            std::snprintf(pj, sizeof pj, "\"pick\": {\"position\": [%.9g, %.9g, %.9g], \"t\": %.9g, \"normal\": [%.9g, %.9g, %.9g], "
+                          "\"face\": %d, \"object_ref\": %llu, \"material_ref\": %llu, \"volume_ref\": %s, \"prim\": %d, \"focus\": %.9g}",
+                          hit.position[0], hit.position[1], hit.position[2], hit.t, hit.normal[0], hit.normal[1], hit.normal[2], hit.face,
+                          (unsigned long long)hit.object_ref, (unsigned long long)hit.material_ref, vol, hit.prim, focus);
+        }
+        std::printf("{%s}\n", pj);
+        std::fflush(stdout);
+        pick_json = std::string(", ") + pj;
+    }
+    if (args.autofocus) {
+        bt_hit hit{};
+        float focus = 0.0f;
+        const int found = bt_scene_pick(scene, camera, &cfg, &rc, args.width, args.height, args.autofocus_x, args.autofocus_y, &hit, &focus);
+        check(found, "bt_scene_pick");
+        if (!found)
+            die("--autofocus: the ray through pixel (" + std::to_string(args.autofocus_x) + ", " + std::to_string(args.autofocus_y) + ") hits nothing");
+        check(bt_scene_set_camera_focus(scene, camera, 1, focus), "bt_scene_set_camera_focus");
+        if (!args.quiet) std::fprintf(stderr, "autofocus: pixel (%u, %u) is %.6g away, focus %.6g\n", args.autofocus_x, args.autofocus_y, hit.t, focus);
+    }
 
     // Buffer::new (buffer.rs:41-50), resident in HBM
     const bool sharded = args.shard_world > 1;
@@ -764,7 +821,7 @@ int main(int argc, char **argv) {
             std::snprintf(ad, sizeof ad, ", \"temporal\": {\"frames\": %ld, \"history_mean\": %.4f, \"history_min\": %.4f}", args.frames,
                           history_mean, history_min);
         std::fprintf(f, "{\"width\": %u, \"height\": %u, \"samples_per_call\": %u, \"subsample\": %u, \"calls\": [%s]%s%s%s}\n", args.width,
-                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (despeckle_json + upscale_json + glare_json + resample_json + compare_json).c_str(), display_json);
+                     args.height, args.samples_per_call, args.subsample, per_call.c_str(), ad, (pick_json + despeckle_json + upscale_json + glare_json + resample_json + compare_json).c_str(), display_json);
         std::fclose(f);
     };
     // with the display or the resample stage: once the frame has been shown

@@ -70,6 +70,7 @@ struct bt_scene {
     DeviceArray<BtRectLA> d_la_rows;
     DeviceArray<int32_t> d_other_rows;
     DeviceArray<float> d_density;
+    DeviceArray<BtQueryRef> d_query_refs;  // ray query extension: one row per row of d_prims (bt_internal.hpp)
     DeviceArray<int32_t> d_lens_prims;     // lens extension: rows of d_prims near the sphere of influence
     bt_lens lens_prims_for{};              // the lens d_lens_prims was built for
     bool lens_prims_valid = false;
@@ -143,6 +144,18 @@ std::vector<BtSphereRow> sphere_rows_of(const std::vector<BtPrim> &pr) {
     return rows;
 }
 
+// BtQueryRef table of the flattened scene (ray query extension): the refs behind each row's object, material and volume index.
+// flatten_scene numbers materials and volumes in the order of the scene's data, each kind on its own.
+std::vector<BtQueryRef> query_refs_of(const bt::Scene &sc, const std::vector<BtPrim> &pr) {
+    std::vector<uint64_t> mat_ref, vol_ref;
+    for (const bt::Data &d : sc.data) (d.kind == bt::DATA_VOLUME ? vol_ref : mat_ref).push_back(d.data_ref);
+    std::vector<BtQueryRef> refs;
+    for (const BtPrim &R : pr)
+        refs.push_back(BtQueryRef{sc.objects[(size_t)R.object].object_ref, mat_ref[(size_t)R.material],
+                                  R.volume >= 0 ? vol_ref[(size_t)R.volume] : ~0ull});
+    return refs;
+}
+
 int ensure_device(bt_scene *s) {
     int rc = ensure_flat(s);
     if (rc) return rc;
@@ -184,6 +197,7 @@ int ensure_device(bt_scene *s) {
         s->rows_generation += 1;                   // (part of the block masks' key)
     }
     BT_HIP(s->d_density.upload(s->flat.density));
+    BT_HIP(s->d_query_refs.upload(query_refs_of(s->scene, s->flat.prims)));
     BT_HIP(s->d_aan_rows.upload(s->flat.aan_rows));
     BT_HIP(s->d_la_rows.upload(s->flat.la_rows));
     BT_HIP(s->d_other_rows.upload(s->flat.other_rows));
@@ -727,6 +741,29 @@ int bt_scene_camera_view(const bt_scene *scene, uint64_t camera_ref, const bt_co
     out->width = width;
     out->height = height;
     out->subsample_n = render->subsample_n;
+    return 0;
+}
+
+int bt_scene_set_camera_focus(bt_scene *scene, uint64_t camera_ref, int has_focus, float focus) {
+    if (!scene) return fail(BT_ERR_INVALID_ARG, "null scene");
+    const int i = scene->scene.object_index(camera_ref);
+    if (i < 0) return fail(BT_ERR_INVALID_REF, "invalid object ref " + std::to_string(camera_ref));
+    bt::Object &o = scene->scene.objects[i];
+    if (o.kind != bt::OBJ_CAMERA) return fail(BT_ERR_NOT_CAMERA, "expected a camera object");
+    if (has_focus && !(std::isfinite(focus) && focus > 0.0f)) return fail(BT_ERR_INVALID_ARG, "the focus must be finite and > 0");
+    // read at launch time (fill_launch), like the aspect ratio: no table holds it.  The block masks depend on it and their key
+    // carries has_focus and focus (bt_cull.hpp MaskKey), so the masks cached under the old focus are not taken again.
+    o.has_focus = has_focus != 0;
+    o.focus = has_focus ? focus : 0.0f;
+    return 0;
+}
+
+int bt_scene_query_tables_internal(bt_scene *scene, const BtPrim **prims, const BtQueryRef **refs, int32_t *n_prims) {
+    const int rc = ensure_device(scene);
+    if (rc) return rc;
+    *prims = scene->d_prims.ptr;
+    *refs = scene->d_query_refs.ptr;
+    *n_prims = (int32_t)scene->flat.prims.size();
     return 0;
 }
 

@@ -37,6 +37,26 @@ struct BtDisplayExpose {
     float p_low, p_high, ev, ev_min, ev_max, adapt;
 };
 
+// The ray query API (bt_query.hip).  One BtQueryRef per row of the primitive table, uploaded next to it: what the
+// row's hit reports besides geometry (UINT64_MAX: no volume).
+struct BtQueryRef {
+    uint64_t object_ref, material_ref, volume_ref;
+};
+struct BtPrim;
+struct BtQueryLaunch {
+    const BtPrim *prims;
+    const BtQueryRef *refs;
+    const bt_ray *rays;
+    bt_hit *hits;
+    int32_t n_prims;
+    uint32_t n;                              // rays, 0 < n < 2^30
+};
+struct BtViewRaysLaunch {
+    btview::View view;
+    uint32_t x0, y0, w, h;                   // the rectangle, inside the view's frame; w * h < 2^30
+    bt_ray *rays;
+};
+
 extern "C" {
 // bt_kernels.hip
 hipError_t bt_launch_render(const BtLaunch *P, int output, unsigned grid, size_t lds_bytes, hipStream_t stream);
@@ -69,7 +89,13 @@ hipError_t bt_launch_display_expose(uint32_t *live, uint32_t *last, BtDisplaySta
                                     hipStream_t stream);
 hipError_t bt_launch_display_show(const float *rgba, uint8_t *out, uint64_t n, uint32_t samples, int color_space, int op,
                                   float iw2, int manual, float ev, BtDisplayState *state, hipStream_t stream);
+// bt_query.hip
+hipError_t bt_launch_query(const BtQueryLaunch *Q, hipStream_t stream);
+hipError_t bt_launch_view_rays(const BtViewRaysLaunch *P, hipStream_t stream);
 // bt_api.cpp
+// The ray query's way to the scene: flattens and uploads the tables if they are stale (BT_ERR_DEVICE without a device) and hands
+// out the device pointers of the primitive table and of its BtQueryRef table.  Touches no render state of the handle.
+int bt_scene_query_tables_internal(bt_scene *scene, const BtPrim **prims, const BtQueryRef **refs, int32_t *n_prims);
 int bt_set_error_internal(int code, const char *msg);      // sets bt_last_error / bt_last_error_code; returns `code`
 int bt_scene_lens_on_internal(const bt_scene *scene);
 // The render half of bt_render_adaptive_device (bt_adapt_api.cpp, which has validated everything).

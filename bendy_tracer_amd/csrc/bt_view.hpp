@@ -72,6 +72,14 @@ BT_VIEW_HD void forward(const View &V, float x, float y, float *d) {
     d[0] = w[0] / l; d[1] = w[1] / l; d[2] = w[2] / l;
 }
 
+// The camera focus that puts the point at distance t along forward(x, y) in the focal plane (bt_scene_pick): the render kernel
+// aims a focused ray at origin + d * (focus / |d_cam.z|) (mod.rs:286-299) with d of unit length, so focus = t |d_cam.z|.
+BT_VIEW_HD float focus_of(const View &V, float x, float y, float t) {
+    const float u = (x + V.cn) * V.pw - 1.0f, v = (y + V.cn) * V.ph - 1.0f;                    // forward()'s lines: local[2] is d_cam.z
+    const float yrot = V.v.xfov * 0.5f * -u, xrot = V.v.yfov * 0.5f * -v;
+    return t * fabsf(-cosf(xrot) * cosf(yrot));
+}
+
 // Inverse map: the pixel coordinates at which the view sees the offset `p` from its origin (P - T for a point, a direction for a
 // point at infinity).  Non-finite for p = 0.
 BT_VIEW_HD void inverse(const View &V, const float *p, float *xf, float *yf) {

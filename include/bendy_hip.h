@@ -874,6 +874,55 @@ int bt_debug_compare_host(const float *test_host, uint32_t test_samples, const f
  * BT_ERR_PARSE; capacity_floats < 4 width height -> BT_ERR_INVALID_ARG. */
 int bt_read_pfm(const char *path, float *rgba_host, size_t capacity_floats, uint32_t *width, uint32_t *height);
 
+/* --- EXTENSION -- NOT IN THE REFERENCE: ray queries -- closest hits for the caller's rays, picking, autofocus ---
+ * "What does this ray hit?", answered by the intersection code the render kernels run: `try_hit` (tracer/mod.rs:389-402) for ray i
+ * with the clip [tmin, tmax] taken from the ray.  Off unless called; changes no render and no stage.
+ *   - objects are visited in ascending ObjectRef and every accepted hit shrinks clip.max; a sphere or a plain rect accepts
+ *     t <= clip.max, a cuboid face only t < clip.max (cuboid.rs:96): among exact ties the later plain object wins, the earlier of
+ *     two cuboids wins, and a rect beats a coplanar cuboid face in either order;
+ *   - `dir` is used as given and never normalised (the sphere quadratic assumes unit length: the caller's business, as it is
+ *     Ray::new's in the reference); position = origin + dir * t;
+ *   - sphere: normal = (position - centre) / radius, flipped and BT_FACE_BACK where dot(dir, normal) >= 0; a sphere that carries a
+ *     volume reports the VOLUME_ faces.  Rect: rect.rs:138-142 (p < 0 is the front).  Nothing marches: volumes are surfaces here;
+ *   - material_ref / volume_ref are the DataRefs of the row that was hit (a cuboid's faces carry their own materials), volume_ref
+ *     UINT64_MAX where there is none; `prim` is the row of bt_scene_export_prims, so a cuboid's face is identifiable;
+ *   - a miss: t = +inf, face = prim = -1, the three refs UINT64_MAX, position and normal 0.  A ray misses if any of its floats
+ *     other than tmax is not finite, if tmax is NaN, or if tmin > tmax; tmax = +inf is allowed. */
+typedef struct { float origin[3]; float tmin; float dir[3]; float tmax; } bt_ray;      /* 32 B */
+/* ray.rs:9-15 in the oracle's numbering; 2 (Face::Volume) exists only inside a march and never appears here */
+enum { BT_FACE_MISS = -1, BT_FACE_FRONT = 0, BT_FACE_BACK = 1, BT_FACE_VOLUME_FRONT = 3, BT_FACE_VOLUME_BACK = 4 };
+typedef struct {
+    float position[3]; float t;
+    float normal[3];   int32_t face;
+    uint64_t object_ref, material_ref;
+    uint64_t volume_ref; int32_t prim; uint32_t reserved;
+} bt_hit;                                                                              /* 64 B */
+/* One kernel on `stream`: hits_device[i] answers rays_device[i], i < n.  Returns the number of rays enqueued and does not
+ * synchronise.  Checked before the device is touched, in this order: NULL scene, rays or hits -> BT_ERR_INVALID_ARG; a pointer
+ * that is not 16-byte aligned, or rays == hits -> BT_ERR_INVALID_ARG; n >= 2^30 -> BT_ERR_INVALID_ARG; a lens set on the scene ->
+ * BT_ERR_UNSUPPORTED (queries are straight rays); n == 0 -> 0, nothing is launched.  A valid call without a device returns
+ * BT_ERR_DEVICE.  The scene's tables are flattened and uploaded if they are stale; no render state of the handle changes. */
+int bt_query_rays_device(bt_scene *scene, const bt_ray *rays_device, uint32_t n, bt_hit *hits_device, void *stream);
+/* One kernel on `stream`, no scene: the rays through the footprint centres (bt_view above; csrc/bt_view.hpp `forward`) of the
+ * pixels x0 <= x < x0 + w, y0 <= y < y0 + h, row-major, into rays_device[w * h]: origin = the view's translation, tmin = clip_min,
+ * tmax = clip_max.  Checked before the device is touched, all BT_ERR_INVALID_ARG: NULL view or rays, or rays not 16-byte aligned;
+ * a view the temporal stage refuses; an empty rectangle; a rectangle that leaves the frame.  Returns the number of rays. */
+int bt_view_rays_device(const bt_view *view, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, bt_ray *rays_device, void *stream);
+/* Synchronous convenience: bt_scene_camera_view, one view ray through pixel (x, y), one query, and the copy back.  Returns 1 for
+ * a hit, 0 for a miss, < 0 on error (the two calls' own, and BT_ERR_INVALID_ARG for a NULL hit or a pixel outside the frame).
+ * `focus` may be NULL; on a hit it receives the camera focus that puts the hit point in the focal plane, t * |d_cam.z| with d_cam
+ * the pixel's camera-space direction: the inverse of the render kernel's `dw * (focus / |d_cam.z|)` (mod.rs:286-299), so it
+ * holds under a scaled camera matrix too. */
+int bt_scene_pick(bt_scene *scene, uint64_t camera_ref, const bt_config *config, const bt_render_config *render, uint32_t width,
+                  uint32_t height, uint32_t x, uint32_t y, bt_hit *hit, float *focus);
+/* Replaces the camera's focus IN PLACE, as bt_scene_set_camera_pose replaces its pose: has_focus == 0 clears it (`focus: null`,
+ * no depth of field).  The saved JSON is not updated.  The cached block masks are keyed by the focus and do not survive the
+ * change.  BT_ERR_INVALID_REF / BT_ERR_NOT_CAMERA as the pose setter; with has_focus set, a focus that is not finite or is <= 0
+ * -> BT_ERR_INVALID_ARG.
+ * Not provided: an any-hit or occlusion variant, host-buffer variants, the lens extension, marching into volumes, sharded
+ * anything, device-side ray generation with lens jitter. */
+int bt_scene_set_camera_focus(bt_scene *scene, uint64_t camera_ref, int has_focus, float focus);
+
 void bt_tuning_default(bt_tuning *out);
 /* NULL restores the defaults.  Returns BT_ERR_INVALID_ARG for a value outside the sets above. */
 int bt_scene_set_tuning(bt_scene *scene, const bt_tuning *tuning);
